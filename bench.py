@@ -23,12 +23,39 @@ matches a float64 autograd truth to < 2e-5 per layer (fp16 hi+lo operand pairs, 
 three MFMAs per product, csrc/trunk_x3.hip; tests/test_x3_engine.py).  The bf16 engine is timed on the same config as
 ``value_bf16``.
 
-Timing: after W warmup updates, ``--windows`` (default 3) back-to-back windows of EXACTLY K updates, each
-bracketed by barrier + synchronize; every window's time is the max over ranks; the reported time is the
-median window (``windows_ms_per_step`` lists all of them, ``spread_pct`` = (max - min) / median).
+Timing: after W warmup updates, ``--windows`` back-to-back windows of EXACTLY K updates, each bracketed by
+barrier + synchronize; every window's time is the max over ranks; the reported time is the median window
+(``windows_ms_per_step`` lists all of them, ``spread_pct`` = (max - min) / median).  A plain run times ONE window,
+so ``--steps K`` is the number of timed updates and ``ms_per_step`` the milliseconds one of them took; ``--full``
+times 3 windows.
 
-Strong scaling (the half of the metric that frames/s cannot show): the default run is weak scaling, P paths
-per GPU.  ``strong_scaling`` additionally times the FIXED 64-path population split over the N ranks
+Plain and full runs: ``bench.py --gpus N --steps K --warmup W`` sets up, warms up, times the K updates, writes its
+outputs if ``--dump-outputs DIR`` is given and prints the result line -- nothing else.  ``--full`` adds everything
+else described below to the same line: 3 windows with per-window telemetry, the bf16 engine, the reference's own
+network, strong scaling and the per-rank shapes, the in-run generations-to-solve seed, the committed
+generations-to-solve records and the background cold build.  The options that tune those parts (``--solve-seconds``,
+``--compare-bf16``, ``--reference-preset``, ``--per-rank-shapes``, ``--no-strong``, ``--no-verify-build``) act only
+with ``--full``.
+
+Outputs: ``--dump-outputs DIR`` writes what the last timed update left with its caller as ``DIR/<name>.npy`` (rank
+0): the master weights after its optimizer step (``params``), the per-path fitness (``fitness``), the genotypes
+after its tournaments (``genotypes``) and the update's statistics (``update_stats``: policy loss, value loss,
+entropy, episodes, agent steps, tournaments, generation).  Seeds are fixed, so the same arguments give the same
+inputs in every run and two builds can be compared array by array; an array over ``DUMP_ARRAY_BYTES`` is stored as
+a fixed seeded sample of its elements.
+
+Reproducible headline: on one GPU the fp32x headline trainer runs in the deterministic mode (weight gradients
+summed as int64 fixed point, order-independent; +1-2 % per update), the mode of every committed solve record, so
+two runs with the same arguments compute the same updates bit for bit and write equal ``params``, ``fitness`` and
+``genotypes`` (the two losses and the entropy in ``update_stats`` are reported only, float32 atomic sums of block
+partials that can differ in the last bits).  ``--atomics`` times
+the float-atomic sums instead: a little faster, but one sampled action that flips on a last-bit difference sends
+the trajectories apart (after 5 + 20 updates on an MI355X two runs of one build differed by 2e-3 in ``params`` and
+4e-4 in ``fitness``, relative L2 norm).  The other engines and the extra trainers of ``--full`` are deterministic
+only with ``--deterministic``, as before.
+
+Strong scaling (the half of the metric that frames/s cannot show; ``--full``): the headline is weak scaling, P
+paths per GPU.  ``strong_scaling`` additionally times the FIXED 64-path population split over the N ranks
 (TrainConfig.paths_total: 64 / N paths per GPU, the same GA over P_total and the same summed gradient, env and
 sampling RNG keyed by the global env index -- tests/test_distributed.py shows 4 ranks reproduce one process),
 i.e. the per-update latency that divides the wall time of a solve (solves take 20-34 K updates whatever the
@@ -39,12 +66,12 @@ config the headline instead.
 
 Steady state: every env's first episode starts at a random late score
 (PongVec.stagger_scores), so fitness windows fill and tournaments fire inside
-the timed window (``generations_in_timed_window``).  After it, one
+the timed window (``generations_in_timed_window``).  After it, with ``--full``, one
 generations-to-solve seed runs on a fresh trainer under a hard wall cap
 (``generations_to_solve_in_run``); ``generations_to_solve`` lists every
 committed multi-seed record of exactly this config (scripts/solve.py).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 ``--gpus N`` > 1 without torchrun's WORLD_SIZE in the environment launches its own N ranks (like the reference's
@@ -53,12 +80,12 @@ CHILD process, started before this process imports torch or touches the GPU; ran
 this process's stdout and the exit code is the launcher's.  Under torchrun, a WORLD_SIZE different from ``--gpus``
 is an error (exit 2), so an N-GPU record can never come from a different number of ranks.
 
-Per-rank strong-scaling shapes (one GPU): the 1-GPU run also times the per-rank shapes of the strong-scaling
+Per-rank strong-scaling shapes (one GPU, ``--full``): the 1-GPU run also times the per-rank shapes of the strong-scaling
 split, P_total / N paths x E envs for N = 2, 4, 8 (3 windows each), and reports ``strong_scaling.per_rank`` with a
 predicted seconds-to-solve per N: committed one-GPU updates-to-solve x (measured per-rank ms + a modelled ring
 all-reduce of the gradient over xGMI).  A prediction, labelled as one.
 
-Build provenance: on one GPU, a cold build of every csrc/*.hip into a scratch directory runs in a niced background
+Build provenance (``--full``): on one GPU, a cold build of every csrc/*.hip into a scratch directory runs in a niced background
 process during the run (``python -m pathnet_gym_amd._build --verify``); ``build.verified`` reports whether the cold
 objects and library are byte-identical to the loaded ones (the build is reproducible: explicit compilation-unit
 ids, relative paths).
@@ -181,6 +208,28 @@ def solve_records(key: dict, n_gpus: int, sources: str = None, root: str = None)
             "criterion": CRITERION}
 
 
+def built_library() -> str:
+    """The HIP library of this run.  Where the tree can be written: _build.build(), which recompiles what is stale.
+    In a tree this user cannot write (built by another user, or read-only): the library that build left, accepted
+    only if its stamp still matches the sources, the flags and its own bytes.  A stale or missing library there is
+    an error, never a fall-back."""
+    import glob
+    import hashlib
+    from pathnet_gym_amd import _build
+    try:
+        return _build.build()
+    except PermissionError as e:
+        denied = e
+    headers = sorted(glob.glob(os.path.join(_build.CSRC, "*.h")))
+    digests = [_build._digest([s] + headers, [_build.HIPCC] + _build.FLAGS + [_build.REPRO])
+               for s in sorted(glob.glob(os.path.join(_build.CSRC, "*.hip")))]
+    if _build._needs(_build.LIB, hashlib.sha256("".join(digests).encode()).hexdigest()):
+        raise RuntimeError(f"{_build.LIB} is missing or does not match csrc/ and cannot be rebuilt here "
+                           f"({denied}); run build() as a user who can write the tree") from denied
+    _build.LAST["compiled"], _build.LAST["relinked"] = [], False
+    return _build.LIB
+
+
 def build_trainer(args, ctx, dtype: str, stagger: bool, paths_total: int = 0):
     """The bench trainer; ``paths_total`` > 0: strong scaling (that population split over the ranks)."""
     from pathnet_gym_amd.config import preset
@@ -227,11 +276,12 @@ def gpu_telemetry() -> dict:
 
 
 def timed_windows(tr, ctx, steps: int, warmup: int, windows: int = 1, markers: bool = False, info=None,
-                  mark_window: int = 0):
+                  mark_window: int = 0, last=None):
     """W untimed updates, then ``windows`` back-to-back windows of EXACTLY K updates, each between barrier +
     synchronize on both sides; a window's time is the max over ranks.  Returns [(seconds, frames, generations)].
     ``info`` (a list): per window, the GPU telemetry sampled while its last updates still run (before the drain) and
-    the population's mean active modules per layer (mutation can grow a path; the work per update follows it)."""
+    the population's mean active modules per layer (mutation can grow a path; the work per update follows it).
+    ``last`` (a dict): receives the UpdateStats of the last timed update under "stats" (dump_outputs)."""
     import torch
 
     def sync():
@@ -254,10 +304,13 @@ def timed_windows(tr, ctx, steps: int, warmup: int, windows: int = 1, markers: b
             _plib.call("launch_prof_marker", 1, _plib.stream())
         host0 = dict(tr.tracer.totals_ms)
         t0 = time.perf_counter()
+        st = None
         for _ in range(steps):
-            tr.update()
+            st = tr.update()
         tel = gpu_telemetry() if info is not None else None
-        tr.flush()                               # drain the pipelined host bookkeeping of the last update
+        st = tr.flush() or st                    # drain the pipelined host bookkeeping of the last update
+        if last is not None:
+            last["stats"] = st
         if markers and w == mark_window:
             _plib.call("launch_prof_marker", 2, _plib.stream())
         sync()
@@ -283,6 +336,42 @@ def window_summary(wins, steps: int) -> dict:
     return {"ms": med, "all": [round(x, 3) for x in ms],
             "spread_pct": round((max(ms) - min(ms)) / med * 100.0, 2) if med > 0 else 0.0,
             "frames": wins[0][1], "generations": sum(w[2] for w in wins)}
+
+
+DUMP_ARRAY_BYTES = 48 << 20       # per array: the weights are the only large one, so a dump stays under 64 MB
+
+
+def dump_outputs(tr, stats, out_dir: str) -> dict:
+    """``--dump-outputs``: what the last timed update left with its caller, as ``out_dir/<name>.npy`` (float32, the
+    statistics float64).  An array over DUMP_ARRAY_BYTES is stored as a fixed sample of its elements (sorted indices
+    drawn once from numpy's default_rng(0), the same in every run and build).  Returns {name: [shape, sampled]}."""
+    import numpy as np
+    import torch
+    eng = tr.engine
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrays = {"params": tr.model.store.flat.detach().float().cpu().numpy()}
+    fitness = eng.fitness if eng is not None else tr.fitness_local
+    arrays["fitness"] = fitness.detach().float().cpu().numpy()
+    if eng is not None and eng.ga_dev is not None:
+        arrays["genotypes"] = eng.ga_dev["geno"].detach().float().cpu().numpy()
+    else:
+        arrays["genotypes"] = np.asarray(tr.pop.genotypes, dtype=np.float32)
+    if stats is not None:
+        arrays["update_stats"] = np.array([stats.loss_pi, stats.loss_v, stats.entropy, stats.episodes, stats.steps,
+                                           stats.tournaments, tr.pop.generation], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        keep = DUMP_ARRAY_BYTES // a.itemsize
+        sampled = a.size > keep
+        if sampled:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = [list(a.shape), sampled]
+    return written
 
 
 def in_run_solve(args, ctx, dtype: str, cap_s: float, paths_total: int = 0) -> dict:
@@ -473,7 +562,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps updates (median reported)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps updates, median reported (default: 1; 3 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: 3 windows with telemetry, the bf16 engine, the "
+                         "reference's own network, strong scaling and per-rank shapes, an in-run generations-to-solve "
+                         "seed, the committed solve records, the background cold build (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed updates, write what the last one computed (weights, fitness, genotypes, "
+                         "statistics) as DIR/<name>.npy")
     ap.add_argument("--paths", type=int, default=64, help="paths per GPU (weak scaling)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="headline: weak (--paths per GPU) or strong (--paths-total split over the GPUs)")
@@ -494,6 +591,9 @@ def main():
                          "hi+lo pairs, 3 MFMAs per product, <= 2e-5 per layer vs a plain fp32 oracle, "
                          "csrc/trunk_x3.hip); fp32: fp32 MFMA operands (csrc/trunk_f32.hip); bf16: bf16 operands")
     ap.add_argument("--deterministic", action="store_true", help="fixed-order gradient reductions (bit-reproducible)")
+    ap.add_argument("--atomics", action="store_true",
+                    help="one GPU, fp32x: sum the headline trainer's weight gradients with float atomics (not "
+                         "reproducible from run to run) instead of the deterministic mode it runs in by default")
     ap.add_argument("--rollout-groups", type=int, default=0,
                     help="path groups stepped on their own streams in the rollout (0 = auto, 1 = one stream)")
     ap.add_argument("--ga-backend", default="device", choices=["device", "host"],
@@ -524,6 +624,9 @@ def main():
     ap.add_argument("--no-verify-build", action="store_true",
                     help="skip the background cold build that checks the loaded library against the sources")
     args = ap.parse_args()
+    full = args.full
+    if args.windows is None:
+        args.windows = 3 if full else 1
     t_start = time.time()
     ws_env = os.environ.get("WORLD_SIZE")
     if ws_env is None and args.gpus > 1:
@@ -533,8 +636,8 @@ def main():
               f"{ws_env} ranks", file=sys.stderr, flush=True)
         sys.exit(2)
     verify_h = None
-    if args.backend == "hip" and int(ws_env or 1) == 1 and not args.no_verify_build and not args.prof_window \
-            and not under_profiler():
+    if full and args.backend == "hip" and int(ws_env or 1) == 1 and not args.no_verify_build \
+            and not args.prof_window and not under_profiler():
         verify_h = start_build_verify()
 
     import torch
@@ -544,7 +647,7 @@ def main():
     build_info = None
     if args.backend == "hip":
         from pathnet_gym_amd import _build
-        build_info = _build.build_info(_build.build())
+        build_info = _build.build_info(built_library())
 
     if args.kernel_opt:
         from pathnet_gym_amd.ops import _lib
@@ -560,17 +663,26 @@ def main():
     head_total = args.paths_total if args.scaling == "strong" else 0
     compare = args.compare_bf16 if args.compare_bf16 is not None else int(single and args.dtype != "bf16")
     stagger = not args.no_stagger
-    cfg, tr = build_trainer(args, ctx, args.dtype, stagger, paths_total=head_total)
+    head_args = args
+    if world == 1 and args.backend == "hip" and args.dtype == "fp32x" and not args.atomics:
+        # the headline and its outputs are the same in every run (the extra trainers of --full keep args as given)
+        head_args = argparse.Namespace(**vars(args))
+        head_args.deterministic = True
+    cfg, tr = build_trainer(head_args, ctx, args.dtype, stagger, paths_total=head_total)
     verified = None
     if verify_h is not None:
         # the cold build (8 niced hipcc jobs) runs while torch imports and the trainer builds; it is joined HERE, so
         # no compiler competes with any timed window
         verified = finish_build_verify(verify_h)
         verify_h = None
-    tele = []
+    tele = [] if full else None          # plain run: no SMI query inside its one timed window
+    last = {}
     wins = timed_windows(tr, ctx, args.steps, args.warmup, args.windows, markers=args.prof_window, info=tele,
-                         mark_window=min(args.prof_window_index, args.windows - 1))
+                         mark_window=min(args.prof_window_index, args.windows - 1), last=last)
     ws = window_summary(wins, args.steps)
+    dumped = None
+    if args.dump_outputs and ctx.is_main:
+        dumped = dump_outputs(tr, last.get("stats"), args.dump_outputs)
     dt = ws["ms"] * args.steps / 1e3
     value = ws["frames"] / dt
     x3 = tr.compute_dtype == "fp32x"
@@ -597,7 +709,6 @@ def main():
         "windows": args.windows,
         "windows_ms_per_step": ws["all"],
         "spread_pct": ws["spread_pct"],
-        "windows_telemetry": tele,
         "data": (f"synthetic: on-device Atari-style {cfg.tasks[0]} simulator (210x160 RGB -> gray 160x120 x4 "
                  "stack), random-init weights") if len(cfg.net.input_shape) == 3 else
                 f"synthetic: on-device {cfg.tasks[0]}, random-init weights",
@@ -625,12 +736,22 @@ def main():
         "generations_in_timed_window": int(wins[0][2]),
         "generations_in_timed_windows": int(ws["generations"]),
     }
+    if tele is not None:
+        rec["windows_telemetry"] = tele
+    if dumped is not None:
+        rec["dumped_outputs"] = dumped
     if build_info is not None:
         rec["build"] = build_info
     if getattr(tr, "precision_note", None):
         rec["precision_note"] = tr.precision_note
     tr_numel = int(tr.model.store.layout.numel)
     del tr
+    if not full:
+        # a plain run ends here: set-up, warm-up, the timed updates, the outputs, the result line
+        if ctx.is_main:
+            print(json.dumps(rec), flush=True)
+        ctx.destroy()
+        return
     if compare:
         _, trb = build_trainer(args, ctx, "bf16", stagger, paths_total=head_total)
         wb = window_summary(timed_windows(trb, ctx, args.steps, args.warmup, args.windows), args.steps)

@@ -18,7 +18,7 @@ relative paths, so the bytes depend only on the sources, the flags and the compi
 not on the checkout path or the output file name (hipcc otherwise derives the
 compilation-unit id from them).  ``python -m pathnet_gym_amd._build --verify`` cold-builds
 every source into a scratch directory and compares each object and the library with the
-shipped ones byte for byte (bench.py runs it on the GPU box, in the background).
+shipped ones byte for byte (bench.py --full runs it in the background).
 """
 from __future__ import annotations
 

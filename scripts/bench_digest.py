@@ -1,4 +1,4 @@
-"""One-screen digest of a bench.py JSON record (the driver's one-GPU command): headline, bf16, reference preset,
+"""One-screen digest of a bench.py --full JSON record (one GPU): headline, bf16, reference preset,
 per-rank strong-scaling shapes, the in-run solve against its committed record, and generations-to-solve.
 
     python scripts/bench_digest.py gpurun_out/.../bench_driver.json

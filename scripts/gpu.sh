@@ -21,7 +21,7 @@
 #   scripts/gpu.sh "rccl P [WINDOWS]"                        forced one-rank RCCL vs no group at P paths, interleaved
 #                                                            (nogroup forced nogroup forced), median windows
 #   scripts/gpu.sh "windows N <bench.py args>"               N back-to-back windows with per-window telemetry
-#   scripts/gpu.sh "driver"                                  the driver's one-GPU bench command (bench.py --gpus 1)
+#   scripts/gpu.sh "driver"                                  the one-GPU bench with every extra measurement (bench.py --gpus 1 --full)
 #
 # Env: OUT (default gpurun_out/r4).
 set -o pipefail
@@ -167,14 +167,14 @@ step_rccl() {
 step_windows() {
   local n=$1; shift
   nb=$((nb + 1))
-  $T 400 python -u bench.py --steps 20 --warmup 5 --windows "$n" --solve-seconds 0 --compare-bf16 0 --per-rank-shapes '' \
+  $T 400 python -u bench.py --full --steps 20 --warmup 5 --windows "$n" --solve-seconds 0 --compare-bf16 0 --per-rank-shapes '' \
       --reference-preset 0 --no-verify-build "$@" > "$OUT/windows_$nb.log" 2>&1 || fail windows $? "$OUT/windows_$nb.log"
   grep '^{' "$OUT/windows_$nb.log" > "$OUT/windows_$nb.json"
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read()); print('windows', d['ms_per_step'], d['windows_ms_per_step']); [print(' ', t.get('ms'), t.get('sclk_mhz'), t.get('power'), t.get('active_modules_max_per_layer'), (t.get('host_ms_per_update') or {}).get('collect')) for t in d['windows_telemetry']]" "$OUT/windows_$nb.json"
 }
 
 step_driver() {
-  $T 800 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.log" 2>&1 || fail driver $? "$OUT/bench_driver.log"
+  $T 800 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver.log" 2>&1 || fail driver $? "$OUT/bench_driver.log"
   grep '^{' "$OUT/bench_driver.log" > "$OUT/bench_driver.json"
   python3 scripts/bench_digest.py "$OUT/bench_driver.json"
 }

@@ -136,7 +136,7 @@ def test_forced_rccl_bench_builds_several_trainers(hip_lib, tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--paths", "16", "--paths-total", "16", "--envs", "16",
            "--tmax", "5", "--steps", "3", "--warmup", "2", "--windows", "2", "--per-rank-shapes", "2",
-           "--solve-seconds", "8", "--compare-bf16", "0", "--no-verify-build"]
+           "--solve-seconds", "8", "--compare-bf16", "0", "--no-verify-build", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
