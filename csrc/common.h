@@ -159,35 +159,67 @@ DEVI uint32_t env_rand_u32(uint32_t seed, uint32_t env_id, uint32_t counter, uin
 // 2^-FX_SHIFT instead (global_atomic_add_x2 / ds_add_u64).  Integer addition is associative, so the sum does not
 // depend on the order in which workgroups or waves arrive; x3_fx_flush converts it back and adds it to the fp32
 // gradient.  fx == nullptr selects the fp32 atomics (the default, non-deterministic mode).
-// Resolution 2^-34 ~ 5.8e-11 absolute per contribution; range guard: a contribution of magnitude >= FX_LIMIT (or a
-// NaN) sets fx[-1], which the flush turns into the fp32x range flag (runtime.guard.X3RangeError) -- with at most 2^13
-// contributions per entry (every kernel here stays below it) the int64 sum cannot wrap.
+// Resolution 2^-34 ~ 5.8e-11 absolute per contribution; with at most 2^13 contributions per entry (every kernel here
+// stays below it) the int64 sum cannot wrap.
+// A contribution that cannot be quantised -- NaN, +-inf, or finite with magnitude >= FX_LIMIT -- never reaches the
+// float -> int64 conversion (undefined for it).  It is dropped from the fixed-point sum and a NaN is added to the fp32
+// gradient entry it was meant for, as the fp32 atomics would have left one there (or an overflow): the optimizer's
+// non-finite check (csrc/optim.hip seg_sqnorm / nonfinite_flag) then skips that update on every rank, or ignores the
+// entry when its segment is frozen, exactly as in the default mode.  The two causes stay apart: a non-finite
+// contribution is a non-finite update and nothing more (TrainConfig.max_nonfinite counts it); a finite one out of
+// range also sets bit 0 of the guard word fx[-1], which the flush turns into the fp32x range flag X3_RANGE_FX
+// (runtime.guard.X3RangeError, fatal: the model's gradients do not fit the fixed-point format).
+// A workgroup's LDS bias partial has no gradient entry yet, so lds_acc marks the slot instead: it is set to
+// FX_LDS_DROPPED = 2^62.  A slot takes fewer than 2^10 contributions (<= 512 threads, a few passes) of magnitude
+// < 2^50, so whatever is added around the mark keeps the slot within 2^62 +- 2^60, and a healthy partial stays below
+// 2^60: "slot >= 2^61" (fx_lds_dropped) tells the two apart, and gacc_q writes the NaN in place of the partial.
 // ---------------------------------------------------------------------------------------------------------------
 #define FX_SHIFT 34
 extern long long* g_fx_accum;      // host side: the accumulator of the backward being launched (csrc/trunk_x3.hip)
 #define FX_LIMIT 65536.f
-DEVI unsigned long long fx_q(float v) { return (unsigned long long)__float2ll_rn(v * 0x1p34f); }
-DEVI void fx_guard(long long* fx, float v) {
-  if (!(fabsf(v) < FX_LIMIT)) atomicOr(reinterpret_cast<unsigned long long*>(fx - 1), 1ull);
-}
+#define FX_GUARD_RANGE 1ull        // fx[-1]: a finite contribution (or LDS partial) left the fixed-point range
+#define FX_LDS_DROPPED (1ull << 62)
+DEVI bool fx_fits(float v) { return fabsf(v) < FX_LIMIT; }          // false for NaN and +-inf too
+DEVI unsigned long long fx_q(float v) { return (unsigned long long)__float2ll_rn(v * 0x1p34f); }   // needs fx_fits(v)
+DEVI void fx_flag_range(long long* fx) { atomicOr(reinterpret_cast<unsigned long long*>(fx - 1), FX_GUARD_RANGE); }
 // grad[i] += v, many writers
 DEVI void gacc(float* grad, long long* fx, long i, float v) {
   if (fx) {
-    fx_guard(fx, v);
-    atomicAdd(reinterpret_cast<unsigned long long*>(fx + i), fx_q(v));
+    const bool fits = fx_fits(v);
+    if (!fits) {
+      if (isfinite(v)) fx_flag_range(fx);
+      atomicAdd(grad + i, __builtin_nanf(""));
+    }
+    atomicAdd(reinterpret_cast<unsigned long long*>(fx + i), fx_q(fits ? v : 0.f));   // dropped: adds 0
   } else {
     atomicAdd(grad + i, v);
   }
 }
-// LDS partial (a workgroup's bias sums): float atomics, or int64 fixed point in the same (8-byte) slots
-DEVI void lds_acc(float* f, unsigned long long* q, int i, float v, bool det) {
-  if (det) atomicAdd(q + i, fx_q(v));
-  else atomicAdd(f + i, v);
+// LDS partial (a workgroup's bias sums): float atomics (fx == nullptr), or int64 fixed point in the same (8-byte)
+// slots; a contribution that cannot be quantised marks its slot (see above)
+DEVI void lds_acc(float* f, unsigned long long* q, int i, float v, long long* fx) {
+  if (!fx) {
+    atomicAdd(f + i, v);
+  } else if (fx_fits(v)) {
+    atomicAdd(q + i, fx_q(v));
+  } else {
+    if (isfinite(v)) fx_flag_range(fx);
+    atomicExch(q + i, FX_LDS_DROPPED);
+  }
 }
-// fx[i] += q (an LDS fixed-point partial, already quantised), with the same range guard
-DEVI void gacc_q(long long* fx, long i, unsigned long long q) {
+DEVI bool fx_lds_dropped(unsigned long long q) { return (long long)q >= (1ll << 61); }
+// fx[i] += q (an LDS fixed-point partial, already quantised), with the same range guard; a marked slot, or a partial
+// out of range, becomes a NaN in grad[i]
+DEVI void gacc_q(float* grad, long long* fx, long i, unsigned long long q) {
   const long long s = (long long)q;
-  if (s >= (1ll << 50) || s <= -(1ll << 50)) atomicOr(reinterpret_cast<unsigned long long*>(fx - 1), 1ull);
+  if (fx_lds_dropped(q)) {
+    atomicAdd(grad + i, __builtin_nanf(""));
+    return;
+  }
+  if (s >= (1ll << 50) || s <= -(1ll << 50)) {
+    fx_flag_range(fx);
+    atomicAdd(grad + i, __builtin_nanf(""));
+  }
   atomicAdd(reinterpret_cast<unsigned long long*>(fx + i), q);
 }
 DEVI float fx_f(unsigned long long q) { return (float)((double)(long long)q * 0x1p-34); }

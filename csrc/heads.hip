@@ -301,20 +301,22 @@ __global__ __launch_bounds__(256) void a2c_grad_kernel(
           H -= z[j] * lp[j];
         }
       const int a = actions[i];
-      float lpa = 0.f;
+      float lpa = 0.f, pa = 1.f;
 #pragma unroll
       for (int j = 0; j < AMAX; ++j)
-        if (j < A && j == a) lpa = lp[j];
+        if (j < A && j == a) { lpa = lp[j]; pa = z[j]; }
       spol += -(lpa * adv + beta * H) * weight;
       sval += vcoef * 0.5f * (R - v) * (R - v) * weight;
       sent += H;
       // d/dz_j [-(log pi_a * adv) - beta*H] = -adv*(1[j==a] - pi_j) + beta*pi_j*(log pi_j + H)
-      // (clip(pi, 1e-20) has zero gradient below 1e-20; negligible, ignored)
+      // clip(pi, 1e-20) has zero gradient below 1e-20: a taken action with pi_a under the clip has a constant log pi_a,
+      // so its advantage term vanishes (adv_g = 0); in the entropy term the clip changes pi_j * 46 < 5e-19, ignored
+      const float adv_g = pa >= 1e-20f ? adv : 0.f;
 #pragma unroll
       for (int j = 0; j < AMAX; ++j)
         if (j < A) {
           const float oh = (j == a) ? 1.f : 0.f;
-          dlogits[i * A + j] = weight * (-adv * (oh - z[j]) + beta * z[j] * (lp[j] + H));
+          dlogits[i * A + j] = weight * (-adv_g * (oh - z[j]) + beta * z[j] * (lp[j] + H));
         }
       dvalue[i] = weight * vcoef * (v - R);
     }

@@ -379,10 +379,10 @@ __global__ __launch_bounds__(256) void lstm_wgrad_x3_kernel(
       }
   if (do_bias) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, sc + c, bpart[c], fx != nullptr);
+    for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, sc + c, bpart[c], fx);
     __syncthreads();
     if (tid < 64) {
-      if (fx) gacc_q(fx, b_off + p0b + tid, dbq[tid]);
+      if (fx) gacc_q(grad, fx, b_off + p0b + tid, dbq[tid]);
       else atomicAdd(&grad[b_off + p0b + tid], dbias[tid]);
     }
   }

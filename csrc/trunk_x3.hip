@@ -1761,7 +1761,7 @@ __global__ __launch_bounds__(256, NCXP <= 2 ? 3 : 2) void conv_wgrad_slab_x3(con
       const int slot = 2 * ct0 + rel;
       if (rel < 2 * NC && slot < cnt) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, slot * 8 + c, acc_b[k][c >> 1][c & 1] * g_scale, fx != nullptr);
+        for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, slot * 8 + c, acc_b[k][c >> 1][c & 1] * g_scale, fx);
       }
     }
   };
@@ -1776,7 +1776,7 @@ __global__ __launch_bounds__(256, NCXP <= 2 ? 3 : 2) void conv_wgrad_slab_x3(con
   __syncthreads();
   if (tid < cnt * 8) {
     const long bi = b_off + (long)mods[tid >> 3] * chunk + (tid & 7);
-    if (fx) gacc_q(fx, bi, dbq[tid]);
+    if (fx) gacc_q(grad, fx, bi, dbq[tid]);
     else atomicAdd(&grad[bi], dbias[tid]);
   }
 }
@@ -1954,7 +1954,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_x3(const bf16_t* __restrict
     }
     if (gact) {
 #pragma unroll
-      for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, (2 * ct0 + gsl) * 8 + c, bpart[c] * g_scale, fx != nullptr);
+      for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, (2 * ct0 + gsl) * 8 + c, bpart[c] * g_scale, fx);
     }
   };
   for (int pass = 0; pass < npass; ++pass) {
@@ -1968,7 +1968,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_x3(const bf16_t* __restrict
   __syncthreads();
   if (tid < cnt * 8) {
     const long bi = b_off + (long)mods[tid >> 3] * chunk + (tid & 7);
-    if (fx) gacc_q(fx, bi, dbq[tid]);
+    if (fx) gacc_q(grad, fx, bi, dbq[tid]);
     else atomicAdd(&grad[bi], dbias[tid]);
   }
 }
@@ -2158,13 +2158,13 @@ __global__ __launch_bounds__(WT3<G>::NT, 2) void conv_wgrad_tile_x3(const uint16
     }
     if (slot_ok) {
 #pragma unroll
-      for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, (2 * ct0 + a_my) * 8 + c, bpart[c] * g_scale, fx != nullptr);
+      for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, (2 * ct0 + a_my) * 8 + c, bpart[c] * g_scale, fx);
     }
   }
   __syncthreads();
   if (tid < cnt * 8 && ((tid >> 5) % (int)gridDim.z) == (int)blockIdx.z) {   // the slots of this workgroup's passes
     const long bi = b_off + (long)mods[tid >> 3] * chunk + (tid & 7);
-    if (fx) gacc_q(fx, bi, dbq[tid]);
+    if (fx) gacc_q(grad, fx, bi, dbq[tid]);
     else atomicAdd(&grad[bi], dbias[tid]);
   }
 }
@@ -4156,13 +4156,13 @@ __global__ __launch_bounds__(256) void fc_wgrad_x3(const bf16_t* __restrict__ X,
       }
   if (do_bias) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, sc + c, bpart[c], fx != nullptr);
+    for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, sc + c, bpart[c], fx);
     __syncthreads();
     if (tid < 64 && n0b + tid < Cout) {
       const long bi = b_off + (long)j * chunk + n0b + tid;
       if (fx) {
-        if (nsplit == 1) grad[bi] = fx_f(dbq[tid]);
-        else gacc_q(fx, bi, dbq[tid]);
+        if (nsplit == 1) grad[bi] = fx_lds_dropped(dbq[tid]) ? __builtin_nanf("") : fx_f(dbq[tid]);
+        else gacc_q(grad, fx, bi, dbq[tid]);
       } else if (nsplit == 1) {
         grad[bi] = dbias[tid];
       } else {
@@ -4257,12 +4257,14 @@ __global__ __launch_bounds__(256) void refresh_x3_all_kernel(const float* __rest
 }
 
 // deterministic mode: grad[i] += fx[i] * 2^-FX_SHIFT and fx[i] = 0 over [n0, n1) (entries no kernel touched stay 0 and
-// are neither read-modified nor written back); fx[-1] (the range guard word) becomes X3_RANGE_FX
+// are neither read-modified nor written back); the guard word fx[-1] is reset and its range bit becomes X3_RANGE_FX.
+// A contribution that could not be quantised (non-finite, or out of range) is already a NaN in its own grad entry
+// (common.h gacc / gacc_q), and "+=" keeps it, so the optimizer skips this update; only the range bit is fatal
 __global__ __launch_bounds__(256) void fx_flush_kernel(long long* __restrict__ fx, float* __restrict__ grad, long n0,
                                                       long n1) {
   if (blockIdx.x == 0 && threadIdx.x == 0 && fx[-1] != 0) {
+    if (fx[-1] & (long long)FX_GUARD_RANGE) atomicOr(&g_x3_range, X3_RANGE_FX);
     fx[-1] = 0;
-    atomicOr(&g_x3_range, X3_RANGE_FX);
   }
   for (long i = n0 + (long)blockIdx.x * 256 + threadIdx.x; i < n1; i += (long)gridDim.x * 256) {
     const long long q = fx[i];

@@ -36,7 +36,11 @@ class X3RangeError(FloatingPointError):
     """fp32x (split fp16 pairs): a value left the fp16 range.  Bit 0 (value 1) of the status: a weight scaled by
     2^8 -- of any trunk layer (x3_refresh_weights) or the LSTM kernel (lstm_refresh_x3) -- reached 32768 (its pair
     no longer represents it); bit 1 (value 2): an activation written as an fp16 pair (trunk or LSTM state) reached
-    65504; bit 2 (value 4, deterministic mode): a weight-gradient contribution left the fixed-point accumulator's range.
+    65504; bit 2 (value 4, deterministic mode): a finite weight-gradient contribution left the fixed-point accumulator's
+    range (|g| >= 65536).  The update that held it is not applied: the contribution becomes a NaN in its gradient
+    entry, so the optimizer's non-finite check skips the step before this error surfaces.  A NaN or inf contribution
+    is not a range error: it is only a non-finite update (skipped, counted by ``NonFiniteGuard``), in deterministic
+    mode as in the default one.
     The status travels in the update's all-reduced counters, so every rank raises together.
 
     Lag: the flags are folded into the counters after each rollout, so an overflow raised by the weight refresh at
@@ -56,8 +60,8 @@ class X3RangeError(FloatingPointError):
             if bits & 2:
                 what.append("an activation stored as an fp16 pair reached 65504")
             if bits & 4:
-                what.append("deterministic mode: a weight-gradient contribution reached the int64 fixed-point range "
-                            "(|g| >= 65536 or NaN, csrc/common.h gacc)")
+                what.append("deterministic mode: a finite weight-gradient contribution reached the int64 fixed-point "
+                            "range (|g| >= 65536, csrc/common.h gacc; that update was skipped)")
         super().__init__(f"fp32x range overflow at update {update}: " + "; ".join(what)
                          + " -- use compute_dtype='fp32' for this model / data scale")
 

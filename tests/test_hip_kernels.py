@@ -301,6 +301,176 @@ def test_heads_and_a2c_grad(hip_lib):
         assert rel(gflat[s.offset:s.offset + s.numel], flat.grad[s.offset:s.offset + s.numel]) < 1e-4, name
 
 
+# ---------------------------------------------------------------------------
+# a2c_grad_kernel (csrc/heads.hip) over its whole switch space, against float64
+# ---------------------------------------------------------------------------
+A2C_GAMMA, A2C_BETA, A2C_VCOEF = 0.99, 0.01, 0.5
+A2C_QUANTITIES = ("dlogits", "dvalue", "policy_loss", "value_loss", "entropy_sum")
+A2C_EPS32 = 2.0 ** -24          # an fp32 result carries this much relative rounding whatever computed it
+# the kernel's error against float64 may be this many times the plain fp32 torch evaluation's (see
+# test_a2c_grad_kernel_vs_float64 for the measured errors behind it)
+A2C_ERR_MULT = 4.0
+A2C_REL_CEILING = 1e-4          # the project's bound for this kernel (test_heads_and_a2c_grad)
+
+
+def _a2c_launch(logits, values, actions, rewards, dones, vboot, lam, rclip, weight):
+    from pathnet_gym_amd.ops import _lib
+    T, B, A = logits.shape
+    dlog = torch.zeros(T, B, A, device=DEV)
+    dval = torch.zeros(T, B, device=DEV)
+    stats = torch.zeros(4, device=DEV)
+    _lib.call("launch_a2c_grad", logits.data_ptr(), values.data_ptr(), actions.data_ptr(), rewards.data_ptr(),
+              dones.data_ptr(), vboot.data_ptr(), T, B, A, A2C_GAMMA, lam, rclip, A2C_BETA, A2C_VCOEF, weight,
+              dlog.data_ptr(), dval.data_ptr(), stats.data_ptr(), _lib.stream())
+    torch.cuda.synchronize()
+    return {"dlogits": dlog, "dvalue": dval, "policy_loss": stats[0], "value_loss": stats[1], "entropy_sum": stats[2]}
+
+
+def _a2c_torch(dtype, logits, values, actions, rewards, dones, vboot, lam, rclip, weight):
+    """algo/a2c_math.py nstep_returns + a2c_loss with autograd, evaluated in ``dtype`` on the same inputs."""
+    T, B, A = logits.shape
+    R, adv = nstep_returns(rewards.to(dtype), values.to(dtype), dones.bool(), vboot.to(dtype), A2C_GAMMA, lam, rclip)
+    lg = logits.to(dtype).reshape(-1, A).clone().requires_grad_(True)
+    vv = values.to(dtype).reshape(-1).clone().requires_grad_(True)
+    wt = torch.full((T * B,), weight, dtype=dtype, device=DEV)
+    loss, lp, lv, ent = a2c_loss(lg, vv, actions.reshape(-1), R.reshape(-1), adv.reshape(-1), A2C_BETA, A2C_VCOEF, wt)
+    loss.backward()
+    out = {"dlogits": lg.grad.reshape(T, B, A), "dvalue": vv.grad.reshape(T, B), "policy_loss": lp, "value_loss": lv,
+           "entropy_sum": ent * (T * B)}
+    # the policy loss is a sum of terms of both signs: its error is measured against the sum of their magnitudes
+    # (the value loss and the entropy are sums of non-negative terms: their own value is that scale)
+    with torch.no_grad():
+        pi = torch.softmax(lg, -1)
+        log_pi = torch.log(pi.clamp(1e-20, 1.0))
+        lp_a = log_pi.gather(1, actions.reshape(-1).long()[:, None]).squeeze(1)
+        entropy = -(pi * log_pi).sum(-1)
+        out["policy_scale"] = (((lp_a * adv.reshape(-1)).abs() + A2C_BETA * entropy) * wt).sum()
+    return out
+
+
+def _a2c_errors(out, ref64):
+    """Relative error of every compared quantity against the float64 reference, computed in float64."""
+    err = {}
+    for k in ("dlogits", "dvalue"):
+        a, b = out[k].double().flatten(), ref64[k].flatten()
+        err[k] = float((a - b).norm() / b.norm())
+    for k, scale in (("policy_loss", "policy_scale"), ("value_loss", "value_loss"), ("entropy_sum", "entropy_sum")):
+        err[k] = abs(float(out[k].double()) - float(ref64[k])) / float(ref64[scale])
+    return err
+
+
+def _a2c_check(label, inputs, lam, rclip, weight):
+    """Launch twice, compare with float64 under a bound tied to the fp32 torch evaluation's own error."""
+    out = _a2c_launch(*inputs, lam, rclip, weight)
+    again = _a2c_launch(*inputs, lam, rclip, weight)
+    ref64 = _a2c_torch(torch.float64, *inputs, lam, rclip, weight)
+    e32 = _a2c_errors(_a2c_torch(torch.float32, *inputs, lam, rclip, weight), ref64)
+    ek = _a2c_errors(out, ref64)
+    for k in A2C_QUANTITIES:
+        print(f"a2c_grad {label} {k}: fp32-torch {e32[k]:.3e} kernel {ek[k]:.3e}")
+    for k in A2C_QUANTITIES:
+        assert bool(torch.isfinite(out[k]).all()), (label, k)
+    # one thread per (t, b) with a fixed arithmetic order: a second launch repeats every per-sample output bit for bit
+    # (the three sums meet in atomics across workgroups and are compared by value only)
+    assert torch.equal(out["dvalue"], again["dvalue"]) and torch.equal(out["dlogits"], again["dlogits"]), label
+    for k in A2C_QUANTITIES:
+        assert ek[k] <= A2C_ERR_MULT * max(e32[k], A2C_EPS32), (label, k, ek[k], e32[k])
+        assert ek[k] < A2C_REL_CEILING, (label, k, ek[k])
+    return out, ref64
+
+
+def _a2c_inputs(T, B, A, seed):
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(T, B, A, generator=g) * 2.0
+    values = torch.randn(T, B, generator=g)
+    vboot = torch.randn(B, generator=g)
+    actions = torch.randint(0, A, (T, B), generator=g, dtype=torch.int32)
+    # non-integer rewards of both signs, magnitudes from 0.05 to 2.5: below and above both clips (0.5 and 1.0)
+    mag = 0.05 + 2.45 * torch.rand(T, B, generator=g)
+    rewards = mag * (torch.randint(0, 2, (T, B), generator=g).float() * 2 - 1)
+    assert float(mag.min()) < 0.5 and ((mag > 0.5) & (mag < 1.0)).any() and float(mag.max()) > 1.0
+    dones = (torch.rand(T, B, generator=g) < 0.2).to(torch.uint8)
+    dones[:, 0] = 0                       # never done: bootstraps from vboot through every step
+    dones[:, 1] = 1                       # done at every step: nothing carries
+    dones[:, 2] = 0
+    dones[0, 2] = 1                       # done only at t = 0
+    dones[:, 3] = 0
+    dones[T - 1, 3] = 1                   # done only at t = T - 1: vboot must not leak into any step
+    return tuple(x.to(DEV).contiguous() for x in (logits, values, actions, rewards, dones, vboot))
+
+
+@pytest.mark.parametrize("T,B,A", [(1, 16, 2), (5, 48, 6), (20, 33, 18)])
+@pytest.mark.parametrize("rclip", [0.0, 1.0, 0.5])
+@pytest.mark.parametrize("lam", [1.0, 0.95, 0.0])
+def test_a2c_grad_kernel_vs_float64(hip_lib, lam, rclip, T, B, A):
+    """launch_a2c_grad over its switches -- the n-step (lam == 1) and GAE (lam != 1) recurrences, the reward clip off
+    / 1.0 / 0.5, A at both ends of AMAX, one partial workgroup / one nearly full / three with a partial last one --
+    against nstep_returns + a2c_loss + autograd in float64.  Columns 0..3 of ``dones`` are never / always / only at
+    t = 0 / only at t = T - 1, the rest random at p = 0.2.
+
+    Bound: the kernel (fast exp / log intrinsics, its own summation order) may be A2C_ERR_MULT times as far from
+    float64 as the same torch code evaluated in fp32 is (with 2^-24 as the floor of that yardstick), and never
+    beyond the project's 1e-4.
+
+    Measured on an MI355X, relative error against float64 (fp32 torch / kernel), per shape the largest over the
+    nine (lam, rclip) settings, and the largest kernel / max(fp32 torch, 2^-24) ratio of any single case:
+        (T, B, A)      dlogits          dvalue           policy loss      value loss       entropy sum
+        (1, 16, 2)     1.2e-7 / 1.0e-7  5.5e-8 / 5.5e-8  3.7e-8 / 9.6e-8  1.4e-7 / 1.4e-7  9.9e-8 / 6.1e-8
+        (5, 48, 6)     9.9e-8 / 7.7e-8  6.6e-8 / 5.5e-8  2.8e-8 / 1.9e-8  8.8e-8 / 1.4e-7  6.8e-8 / 6.8e-8
+        (20, 33, 18)   1.1e-7 / 1.0e-7  8.0e-8 / 8.4e-8  9.0e-9 / 8.9e-9  5.7e-8 / 8.8e-8  1.2e-7 / 1.3e-8
+        worst ratio    1.03             1.05             1.61             2.34             1.00
+    The kernel is as close to float64 as fp32 torch is; the per-sample outputs never exceed its error by more than
+    5 %.  The three sums are single numbers, so a ratio of two roundings of a few 2^-24 each moves by chance (2.34
+    at worst, both errors below 1.5e-7).  A2C_ERR_MULT = 4 leaves that room and no more: a wrong nd factor, carry or
+    clip changes a result by 1e-2 or more."""
+    inputs = _a2c_inputs(T, B, A, seed=1000 * T + A)
+    _a2c_check(f"T{T} B{B} A{A} lam{lam} rclip{rclip}", inputs, lam, rclip, 1.0 / 16)
+
+
+def test_a2c_grad_kernel_extreme_logits(hip_lib):
+    """Softmax edges of a2c_grad_kernel: rows whose logits spread over ~60 (three of six pi_j below the 1e-20 clip of
+    log(clip(pi)), taken actions on both sides of it), rows of equal logits, and the same rows offset by +80 and -80.
+    The logits are multiples of 2^-10, so the offset rows hold exactly logit + 80: after the max subtraction they are
+    the same numbers, and every per-sample output must repeat the un-offset rows bit for bit.  Same float64
+    reference and bound as test_a2c_grad_kernel_vs_float64 (a2c_loss clamps, and autograd gives the clamp's zero
+    gradient).
+
+    Measured on an MI355X (fp32 torch / kernel, lam = 1.0 and 0.95): dlogits 5.9e-8 / 6.3e-8 and 8.4e-8 / 7.8e-8,
+    dvalue 3.2e-8 / 3.2e-8 and 5.1e-8 / 5.9e-8, policy loss 1.7e-8 / 9.9e-9 and 4.9e-8 / 3.4e-8, value loss 8.7e-8 /
+    5.9e-8 and 3.6e-8 / 3.6e-8, entropy sum 1.1e-7 / 1.1e-7 in both; worst ratio 1.06.  Before the kernel dropped the
+    advantage term of a taken action whose pi_a is under the clip (where log(clip(pi_a)) is constant), its dlogits
+    were off by a relative 1.06 here."""
+    T, A, nb = 3, 6, 16
+    g = torch.Generator().manual_seed(7)
+    spread = torch.tensor([0.0, -10.0, -30.0, -50.0, -55.0, -60.0])
+    base = torch.zeros(T, nb, A)
+    for b in range(12):
+        base[:, b] = torch.roll(spread, b % A)
+    base[:, :12] += torch.randint(-256, 257, (T, 12, A), generator=g).float() / 1024     # +-0.25: far from the clip
+    base[:, 12:] = torch.tensor([0.0, 0.703125, -3.5, 17.25])[None, :, None]             # rows of equal logits
+    logits = torch.cat([base, base + 80.0, base - 80.0], 1)
+    assert torch.equal(logits[:, nb:2 * nb] - 80.0, base) and torch.equal(logits[:, 2 * nb:] + 80.0, base)
+    B = 3 * nb
+    rep = lambda x: torch.cat([x, x, x], -1)
+    values = rep(torch.randn(T, nb, generator=g))
+    vboot = rep(torch.randn(nb, generator=g))
+    rewards = rep(torch.randn(T, nb, generator=g) * 1.5)
+    dones = rep((torch.rand(T, nb, generator=g) < 0.2).to(torch.uint8))
+    # column b (spread rolled by b), step t takes action (2b + t) % A, the spread's entry (b + t) % A: all six of
+    # them over the columns, clipped ones included
+    actions = rep(((2 * torch.arange(nb)[None, :] + torch.arange(T)[:, None]) % A).to(torch.int32))
+    pi = torch.softmax(logits.double(), -1)
+    taken = pi.gather(-1, actions.long()[..., None])
+    assert int((pi[:, :12] < 1e-21).sum(-1).min()) == 3 and not ((pi > 1e-21) & (pi < 1e-19)).any()
+    assert (taken < 1e-21).any() and (taken > 1e-19).any()
+    inputs = tuple(x.to(DEV).contiguous() for x in (logits, values, actions, rewards, dones, vboot))
+    for lam in (1.0, 0.95):
+        out, _ = _a2c_check(f"extreme lam{lam}", inputs, lam, 1.0, 1.0 / 16)
+        for k in ("dlogits", "dvalue"):
+            for off in (1, 2):
+                assert torch.equal(out[k][:, off * nb:(off + 1) * nb], out[k][:, :nb]), (lam, k, off)
+
+
 @pytest.mark.parametrize("A,F", [(18, 256), (6, 96), (3, 64), (6, 256), (8, 128)])
 def test_heads_fwd_action_and_feature_widths(hip_lib, A, F):
     """Lane-per-sample heads forward for A <= 8 and A <= 18 (and the 16-samples-per-workgroup form for A <= 8,

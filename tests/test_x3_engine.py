@@ -985,6 +985,210 @@ def test_x3_deterministic_200_updates_bit_identical(hip_lib):
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]) and a[3] == b[3]
 
 
+def _small_x3_trainer(deterministic: bool):
+    """The _det_rollout shape (packed stacks, no graph) with the non-finite policy set: up to 5 skipped updates."""
+    from pathnet_gym_amd.algo.trainer import PathNetTrainer
+    cfg = preset("pong")
+    cfg.paths, cfg.envs_per_path, cfg.a2c.t_max = 3, 16, 4
+    cfg.use_graph = False
+    cfg.compute_dtype = "fp32x"
+    cfg.deterministic = deterministic
+    cfg.max_nonfinite = 5
+    tr = PathNetTrainer(cfg, device=DEV)
+    assert tr.model.hip.fx_det == deterministic and not tr.engine.use_graph
+    # the range flags are one word per process (csrc/trunk_x3.hip g_x3_range): drop what a test that failed before
+    # this one may have left behind, so that each test here answers for its own flags only
+    tr.model.hip.fold_x3_status(torch.zeros(1, device=DEV))
+    return tr
+
+
+def test_x3_fx_flush_known_accumulator_contents(hip_lib):
+    """x3_fx_flush on accumulator contents written by hand: inside [n0, n1) grad becomes grad0 + fp32(q * 2^-34) (the
+    int64 -> float64 -> fp32 conversion, then one fp32 add; numpy does the same) and the accumulator reads zero;
+    outside, both are untouched, including non-zero accumulator entries right before n0 and at n1, which a second
+    and third flush then take.  The window is wider than the launch's 2048 x 256 threads, so the grid-stride loop
+    wraps; neither end is a multiple of 256.  The guard word: set, it is cleared by the flush and surfaces as the
+    fixed-point X3RangeError; clear, the status check passes."""
+    from pathnet_gym_amd.runtime.guard import X3RangeError
+    tr = _small_x3_trainer(True)
+    hip = tr.model.hip
+    fx = hip._fxbuf                                # [0]: guard word; entry i at [1 + i]
+    numel = fx.numel() - 1
+    stride = 2048 * 256                            # threads of the largest flush launch
+    n0, n1 = 1037, 1037 + stride + 5003
+    assert 0 < n0 < n1 < numel - 2 and n0 % 256 and n1 % 256 and int(fx.abs().sum()) == 0
+    rng = np.random.RandomState(5)
+    special = np.array([0, 1, -1, 1 << 34, -(1 << 34), 40 * (1 << 34) + 1, (1 << 50) - 1, -((1 << 50) - 1), 1 << 62,
+                        -(1 << 62)], dtype=np.int64)
+    q = np.zeros(numel, dtype=np.int64)
+    g0 = np.zeros(numel, dtype=np.float32)
+    # the special values at the window's start, around the point where the loop wraps, and at its end; random ones
+    # scattered over the whole window
+    for at in (n0, n0 + stride - 5, n1 - len(special)):
+        q[at:at + len(special)] = special
+    pos = n0 + rng.choice(n1 - n0, 400, replace=False)
+    pos = pos[q[pos] == 0]
+    q[pos] = rng.randint(-(1 << 50), 1 << 50, size=len(pos), dtype=np.int64)
+    # start values: zero, ordinary, negative, and far larger than the increment (which is then absorbed)
+    g0[n0 - 8:n1 + 8] = rng.randn(n1 - n0 + 16).astype(np.float32)
+    g0[pos[:100]] = 0.0
+    g0[pos[100:200]] = -np.abs(g0[pos[100:200]]) - 1.0
+    g0[pos[200:300]] = 1e12
+    g0[n0:n0 + len(special)] = np.float32(3.25)
+    q[n0 - 2], q[n0 - 1], q[n1], q[n1 + 1] = 3 << 34, -(1 << 20), 5 << 33, (1 << 50) - 1     # just outside the window
+    inc = (q.astype(np.float64) * 2.0 ** -34).astype(np.float32)
+
+    def expect(g, lo, hi):
+        e = g.copy()
+        nz = np.zeros(numel, dtype=bool)
+        nz[lo:hi] = q[lo:hi] != 0                  # the kernel leaves entries whose accumulator is zero alone
+        e[nz] = g[nz] + inc[nz]                    # one fp32 add
+        return e
+
+    def bits(t):
+        return t.view(torch.int32)
+
+    fx[1:].copy_(torch.from_numpy(q))
+    grad = torch.from_numpy(g0).to(DEV)
+    hip.fx_end(grad, n0, n1)
+    torch.cuda.synchronize()
+    e1 = expect(g0, n0, n1)
+    assert torch.equal(bits(grad), bits(torch.from_numpy(e1).to(DEV)))
+    left = q.copy()
+    left[n0:n1] = 0
+    assert torch.equal(fx[1:].cpu(), torch.from_numpy(left)) and int(fx[0]) == 0
+    hip.check_x3_status()                          # guard word clear: nothing raised
+    hip.fx_end(grad, n0 - 2, n0)                   # the entries left just outside, each side on its own
+    hip.fx_end(grad, n1, n1 + 2)
+    torch.cuda.synchronize()
+    e2 = expect(expect(e1, n0 - 2, n0), n1, n1 + 2)
+    assert torch.equal(bits(grad), bits(torch.from_numpy(e2).to(DEV)))
+    assert int(fx.abs().sum()) == 0
+    # guard word
+    fx[0] = 1
+    hip.fx_end(grad, n0, n1)
+    torch.cuda.synchronize()
+    assert int(fx[0]) == 0 and torch.equal(bits(grad), bits(torch.from_numpy(e2).to(DEV)))
+    with pytest.raises(X3RangeError, match="fixed-point range"):
+        hip.check_x3_status()
+    hip.check_x3_status()                          # the flag was consumed
+
+
+def _poison_heads_bwd(monkeypatch, tr, poison, path=1):
+    """Wrap this trainer's heads backward: after the real call, write ``poison`` into one element [r, c] of the dfeat
+    it was given (the last trunk layer's output gradient), r a row of ``path`` and c a column whose ReLU bit is set in
+    every module that path has active in the last layer (a masked element would not reach any of them).  The heads'
+    own gradients stay finite; the last layer's weight gradient (gacc), bias gradient (lds_acc / gacc_q) and the input
+    gradient below take the poison through the real kernels.  Returns the dict the wrapper fills: mods, r, c."""
+    eng, hip, model = tr.engine, tr.model.hip, tr.model
+    L, M = len(hip.geoms), hip.M
+    T, B, E = eng.T, eng.B, eng.E
+    real = hip.heads_bwd
+    info = {}
+
+    def wrapped(feat, dlogits, dvalue, grad_flat, dfeat, *args, **kw):
+        out = real(feat, dlogits, dvalue, grad_flat, dfeat, *args, **kw)
+        assert dfeat.data_ptr() == eng.grads[L - 1].data_ptr() and dfeat.dtype == torch.float32
+        cnt = int(model.act_cnt.view(-1)[path * L + L - 1])
+        assert cnt > 0
+        mods = model.act_idx.view(-1)[(path * L + L - 1) * M:(path * L + L - 1) * M + cnt].tolist()
+        words = eng.bits[L - 1][:cnt].to(torch.int32) & 0xFFFF                        # [slot, row, Cout / 16]
+        on = ((words[..., None] >> torch.arange(16, device=DEV)) & 1).bool().flatten(2).all(0)   # [row, Cout]
+        rows = torch.tensor([t * B + path * E + e for t in range(T) for e in range(E)], device=DEV)
+        hit = on[rows].nonzero()
+        assert len(hit) > 0, "no element of the path is unmasked in all of its modules"
+        r, c = int(rows[hit[0, 0]]), int(hit[0, 1])
+        dfeat[r, c] = poison
+        info.update(mods=mods, r=r, c=c)
+        return out
+
+    monkeypatch.setattr(hip, "heads_bwd", wrapped)
+    return info
+
+
+def _opt_state(tr):
+    return [t.detach().clone() for t in (tr.model.store.flat, tr.opt.ms, tr.opt.mom)]
+
+
+def _same_bits(a, b):
+    return all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
+
+
+def _segment(tr, g, name):
+    s = tr.model.store.layout.by_name[name]
+    return g[s.offset:s.offset + s.numel]
+
+
+@pytest.mark.parametrize("poison", [float("nan"), float("inf")], ids=["nan", "inf"])
+@pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "deterministic"])
+def test_x3_poisoned_backward_skips_the_step(hip_lib, monkeypatch, deterministic, poison):
+    """A NaN / inf entering the HIP trunk backward (not written into grad_flat by hand) is a non-finite update in both
+    accumulation modes: the last layer's weight and bias gradients of every module on the poisoned row's path are
+    non-finite before the optimizer, the step is skipped with weights and RMSProp slots bit-unchanged, no
+    X3RangeError follows (it is not a range problem), the next clean update is applied, and the same poisoned update
+    run through PathNetTrainer.update() is reported as skipped under max_nonfinite.  Deterministic mode: the
+    fixed-point accumulator is left zero and the heads' gradients are finite -- the skip came from the trunk path."""
+    tr = _small_x3_trainer(deterministic)
+    eng, hip = tr.engine, tr.model.hip
+    L = len(hip.geoms)
+    tr.update()
+    info = _poison_heads_bwd(monkeypatch, tr, poison)
+    before = _opt_state(tr)
+    eng._rollout_backward_body()
+    torch.cuda.synchronize()
+    g = eng.grad_flat.clone()
+    for j in info["mods"]:
+        for kind in ("weight", "bias"):
+            assert not bool(torch.isfinite(_segment(tr, g, f"layer{L - 1}.module{j}.{kind}")).all()), (j, kind)
+    if deterministic:
+        assert int(hip._fxbuf.abs().sum()) == 0
+        for name in ("policy.weight", "policy.bias", "value.weight", "value.bias"):
+            assert bool(torch.isfinite(_segment(tr, g, name)).all()), name
+    eng.optimizer_step(tr.last_lr)
+    torch.cuda.synchronize()
+    assert float(eng.opt_status) == 1.0
+    assert _same_bits(_opt_state(tr), before)
+    hip.check_x3_status()                          # non-finite is not a range error
+    monkeypatch.undo()
+    st = tr.update()                               # a clean update: applied
+    torch.cuda.synchronize()
+    assert not st.skipped and float(eng.opt_status) == 0.0
+    assert not torch.equal(tr.model.store.flat, before[0])
+    # the same through the trainer: skipped and counted, nothing raised
+    _poison_heads_bwd(monkeypatch, tr, poison)
+    before = _opt_state(tr)
+    st = tr.update()
+    last = tr.flush()
+    monkeypatch.undo()
+    assert st.skipped or (last is not None and last.skipped)
+    assert tr.guard.skipped == 1 and _same_bits(_opt_state(tr), before)
+    hip.check_x3_status()
+
+
+@pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "deterministic"])
+def test_x3_out_of_range_gradient(hip_lib, monkeypatch, deterministic):
+    """A finite 1e30 entering the trunk backward.  Deterministic mode: its contributions do not fit the fixed-point
+    format (|g| >= 65536); they must not be quantised, the step is not applied, and the fatal X3RangeError names the
+    fixed-point range.  Atomic mode: the squared norm overflows and clip_by_norm scales the segment to zero (as
+    test_rmsprop_kernel_matches_torch pins down), so only finite weights are asserted."""
+    from pathnet_gym_amd.runtime.guard import X3RangeError
+    tr = _small_x3_trainer(deterministic)
+    eng, hip = tr.engine, tr.model.hip
+    tr.update()
+    _poison_heads_bwd(monkeypatch, tr, 1e30)
+    before = _opt_state(tr)
+    eng._rollout_backward_body()
+    eng.optimizer_step(tr.last_lr)
+    torch.cuda.synchronize()
+    monkeypatch.undo()
+    assert bool(torch.isfinite(tr.model.store.flat).all())
+    if deterministic:
+        assert float(eng.opt_status) == 1.0 and _same_bits(_opt_state(tr), before)
+        assert int(hip._fxbuf.abs().sum()) == 0
+        with pytest.raises(X3RangeError, match="fixed-point range"):
+            hip.check_x3_status()
+
+
 def test_device_lr_schedule_matches_host_anneal(hip_lib):
     """The optimizer tail advances the lr anneal on device (csrc/ga.hip opt_tail_kernel): after every update the lr
     waiting for the next one equals the host's anneal_lr (fp32) at the next clock, and no host fill was needed."""
