@@ -6,8 +6,12 @@
 //                mutation of the winner's genotype (reference operator, pathnet.py:50-63);
 //                all candidates -> pending; freed slots redraw B disjoint non-busy paths.
 //                Runs inside the optimizer hipGraph right after the fitness all-reduce.
-//  ga_compact  : expressed = genotype | frozen for the rank's local paths -> the kernels'
-//                mask / act_idx / act_cnt and the module-major inverse lists (in place).
+//                MUT 1: the local-shift operator instead (pathnet.py:32-48, counter_mutation_down):
+//                an active module that moves lands 1..4 modules lower, clamped to the layer.
+//  ga_compact  : expressed = genotype | frozen (frozen_or 1, the reference) or the genotype alone
+//                (frozen_or 0: frozen modules stay available, never forced) for the rank's local
+//                paths -> the kernels' mask / act_idx / act_cnt and the module-major inverse lists
+//                (in place).
 #include "common.h"
 
 #define GA_MAXC 64
@@ -22,6 +26,7 @@ DEVI uint32_t ga_rand(uint32_t seed, uint32_t gen, uint32_t x, uint32_t y, uint3
   return wang_hash(h ^ (((y & 0xFFFFu) << 16) + (z & 0xFFFFu)));
 }
 
+template <int MUT>
 __global__ __launch_bounds__(256) void ga_step_kernel(uint8_t* __restrict__ geno, float* __restrict__ fitness,
                                                       int* __restrict__ slots, long long* __restrict__ gen_ctr,
                                                       int* __restrict__ events, int P, int L, int M, int N, int B,
@@ -71,14 +76,29 @@ __global__ __launch_bounds__(256) void ga_step_kernel(uint8_t* __restrict__ geno
     uint8_t g[GA_MAXM];
     for (int m = 0; m < M; ++m) g[m] = geno[((long)w * L + l) * M + m];
     const uint32_t gen = (uint32_t)gen_of[c];
-    for (int m = 0; m < M; ++m) {
-      const uint32_t h0 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m));
-      const uint32_t h1 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m + 1));
-      const long long u24 = (long long)(h0 >> 8);
-      if (g[m]) {
-        if (u24 * ka < (1ll << 25)) { g[m] = 0; g[h1 % (uint32_t)M] = 1; }
-      } else if (u24 * ki < (1ll << 25)) {
-        g[h1 % (uint32_t)M] = 1;
+    if (MUT == 0) {
+      for (int m = 0; m < M; ++m) {
+        const uint32_t h0 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m));
+        const uint32_t h1 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m + 1));
+        const long long u24 = (long long)(h0 >> 8);
+        if (g[m]) {
+          if (u24 * ka < (1ll << 25)) { g[m] = 0; g[h1 % (uint32_t)M] = 1; }
+        } else if (u24 * ki < (1ll << 25)) {
+          g[h1 % (uint32_t)M] = 1;
+        }
+      }
+    } else {
+      // down: only active modules draw; a target is always below m, so it is never walked again
+      for (int m = 0; m < M; ++m) {
+        if (!g[m]) continue;
+        const uint32_t h0 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m));
+        if ((long long)(h0 >> 8) * ka >= (1ll << 25)) continue;
+        const uint32_t h1 = ga_rand(seed, gen, (uint32_t)i, (uint32_t)l, (uint32_t)(2 * m + 1));
+        int t = m - 4 + (int)(h1 & 3u);
+        t = t < 0 ? 0 : t;
+        t = t > M - 1 ? M - 1 : t;
+        g[m] = 0;
+        g[t] = 1;
       }
     }
     for (int m = 0; m < M; ++m) geno[((long)i * L + l) * M + m] = g[m];
@@ -128,15 +148,16 @@ __global__ __launch_bounds__(256) void ga_step_kernel(uint8_t* __restrict__ geno
 
 // expressed masks + compacted lists for paths [p_off, p_off + P_local)
 __global__ void ga_compact_paths_kernel(const uint8_t* __restrict__ geno, const uint8_t* __restrict__ frozen,
-                                        int p_off, int P_local, int L, int M, float* __restrict__ mask,
-                                        int* __restrict__ act_idx, int* __restrict__ act_cnt) {
+                                        int p_off, int P_local, int L, int M, int frozen_or,
+                                        float* __restrict__ mask, int* __restrict__ act_idx,
+                                        int* __restrict__ act_cnt) {
   const int item = blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= P_local * L) return;
   const int p = item / L, l = item - p * L;
   const uint8_t* g = geno + ((long)(p_off + p) * L + l) * M;
   int n = 0;
   for (int m = 0; m < M; ++m) {
-    const int e = (g[m] | frozen[l * M + m]) ? 1 : 0;
+    const int e = (g[m] | (frozen_or ? frozen[l * M + m] : 0)) ? 1 : 0;
     mask[((long)p * L + l) * M + m] = (float)e;
     if (e) act_idx[((long)p * L + l) * M + n++] = m;
   }
@@ -271,25 +292,41 @@ int launch_inv_group(const int* inv_path, const int* inv_slot, const int* inv_cn
   return (int)hipGetLastError();
 }
 
+int launch_ga_step_ex(void* geno, float* fitness, int* slots, long long* gen_ctr, int* events, int P, int L, int M,
+                      int N, int B, int C, unsigned seed, int mut_kind, void* reset, hipStream_t stream) {
+  if (P <= 0 || L <= 0 || M <= 0 || N <= 0 || B <= 0 || C <= 0 || mut_kind < 0 || mut_kind > 1) return -22;
+  if (C > GA_MAXC || B > GA_MAXB || L > GA_MAXL || M > GA_MAXM || C < 1) return -1;
+  if (mut_kind == 1)
+    ga_step_kernel<1><<<1, 256, (size_t)P, stream>>>((uint8_t*)geno, fitness, slots, gen_ctr, events, P, L, M, N, B, C,
+                                                     seed, (uint8_t*)reset);
+  else
+    ga_step_kernel<0><<<1, 256, (size_t)P, stream>>>((uint8_t*)geno, fitness, slots, gen_ctr, events, P, L, M, N, B, C,
+                                                     seed, (uint8_t*)reset);
+  return (int)hipGetLastError();
+}
+
 int launch_ga_step(void* geno, float* fitness, int* slots, long long* gen_ctr, int* events, int P, int L, int M,
                    int N, int B, int C, unsigned seed, void* reset, hipStream_t stream) {
-  if (P <= 0 || L <= 0 || M <= 0 || N <= 0 || B <= 0 || C <= 0) return -22;
-  if (C > GA_MAXC || B > GA_MAXB || L > GA_MAXL || M > GA_MAXM || C < 1) return -1;
-  ga_step_kernel<<<1, 256, (size_t)P, stream>>>((uint8_t*)geno, fitness, slots, gen_ctr, events, P, L, M, N, B, C,
-                                                seed, (uint8_t*)reset);
+  return launch_ga_step_ex(geno, fitness, slots, gen_ctr, events, P, L, M, N, B, C, seed, 0, reset, stream);
+}
+
+int launch_ga_compact_ex(const void* geno, const void* frozen, int p_off, int P_local, int L, int M, int frozen_or,
+                         float* mask, int* act_idx, int* act_cnt, int* inv_path, int* inv_slot, int* inv_cnt,
+                         hipStream_t stream) {
+  if (P_local <= 0 || L <= 0 || M <= 0 || p_off < 0 || frozen_or < 0 || frozen_or > 1) return -22;
+  if (M > GA_MAXM) return -1;
+  const int n1 = P_local * L;
+  ga_compact_paths_kernel<<<(n1 + 255) / 256, 256, 0, stream>>>((const uint8_t*)geno, (const uint8_t*)frozen, p_off,
+                                                                P_local, L, M, frozen_or, mask, act_idx, act_cnt);
+  if (inv_path) {
+    ga_compact_inverse_kernel<<<L * M, 64, 0, stream>>>(mask, P_local, L, M, inv_path, inv_slot, inv_cnt);
+  }
   return (int)hipGetLastError();
 }
 
 int launch_ga_compact(const void* geno, const void* frozen, int p_off, int P_local, int L, int M, float* mask,
                       int* act_idx, int* act_cnt, int* inv_path, int* inv_slot, int* inv_cnt, hipStream_t stream) {
-  if (P_local <= 0 || L <= 0 || M <= 0 || p_off < 0) return -22;
-  if (M > GA_MAXM) return -1;
-  const int n1 = P_local * L;
-  ga_compact_paths_kernel<<<(n1 + 255) / 256, 256, 0, stream>>>((const uint8_t*)geno, (const uint8_t*)frozen, p_off,
-                                                                P_local, L, M, mask, act_idx, act_cnt);
-  if (inv_path) {
-    ga_compact_inverse_kernel<<<L * M, 64, 0, stream>>>(mask, P_local, L, M, inv_path, inv_slot, inv_cnt);
-  }
-  return (int)hipGetLastError();
+  return launch_ga_compact_ex(geno, frozen, p_off, P_local, L, M, 1, mask, act_idx, act_cnt, inv_path, inv_slot,
+                              inv_cnt, stream);
 }
 }

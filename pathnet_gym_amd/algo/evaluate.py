@@ -12,6 +12,7 @@ import torch
 
 from ..envs.registry import make
 from ..models.acnet import ACPathNet
+from .ga import express
 
 
 @torch.no_grad()
@@ -55,8 +56,7 @@ def evaluate_checkpoint(cfg, path: str, episodes: int = 1, max_steps: int = 2000
     with torch.no_grad():
         for s in st.layout.segments:
             st.flat[s.offset:s.offset + s.numel].copy_(d[s.name].reshape(-1))
-    expr = ((g > 0.5) | (fr[None] > 0.5)).astype(np.float32)
-    model.set_paths(expr)
+    model.set_paths(express(g, fr[None], getattr(cfg.ga, "frozen_mode", "or")))
     task = int(d["train.task_idx"][0])
     model.task = task
     env_id = cfg.tasks[min(task, len(cfg.tasks) - 1)]

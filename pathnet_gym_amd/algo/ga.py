@@ -11,7 +11,9 @@ Exact semantics of the reference (``pathnet.py:32-87``, ``doom_pathnet.py:211-29
 * tournament: sample B distinct candidates; once all have a fitness
   (!= -1000) the argmax wins, every loser becomes ``mutation(copy(winner))``,
   ALL B fitness values reset to -1000, a new B is drawn.
-* expressed mask = genotype OR frozen path.
+* expressed mask = genotype OR frozen path (``frozen_mode="or"``); with
+  ``frozen_mode="available"`` (the PathNet paper's rule) it is the genotype
+  alone: a frozen module is used only where a later path selects it.
 
 The whole GA state (genotype table, fitness vector, candidate sets, RNG) is
 replicated on every rank; all ranks feed identical fitness vectors (from the
@@ -89,8 +91,21 @@ def decode_path(g: np.ndarray) -> List[np.ndarray]:
     return [np.where(row == 1.0)[0] for row in np.asarray(g, dtype=np.float32)]
 
 
-def express(g: np.ndarray, frozen: np.ndarray) -> np.ndarray:
-    """Expressed mask = genotype OR frozen path (doom_pathnet.py:216-221,261-266)."""
+FROZEN_MODES = ("or", "available")
+
+
+def check_frozen_mode(frozen_mode: str) -> str:
+    if frozen_mode not in FROZEN_MODES:
+        raise ValueError(f"frozen_mode {frozen_mode!r}: expected one of {FROZEN_MODES}")
+    return frozen_mode
+
+
+def express(g: np.ndarray, frozen: np.ndarray, frozen_mode: str = "or") -> np.ndarray:
+    """Expressed mask.  "or": genotype OR frozen path (doom_pathnet.py:216-221,261-266).  "available": the genotype
+    alone -- a frozen module is used only by a path that selects it (the PathNet paper's rule); it is never trained
+    either way."""
+    if check_frozen_mode(frozen_mode) == "available":
+        return (np.asarray(g) > 0.5).astype(np.float32)
     return ((np.asarray(g) > 0.5) | (np.asarray(frozen) > 0.5)).astype(np.float32)
 
 
@@ -118,6 +133,7 @@ class Population:
     seed: int = 1
     mutation_kind: str = "ref"
     concurrent: int = 1
+    frozen_mode: str = "or"                          # "or" (reference) | "available" (paper): see express()
     genotypes: np.ndarray = field(init=False)        # [P, L, M] float32 {0,1}, evolvable part
     frozen: np.ndarray = field(init=False)           # [L, M] float32 union of frozen paths
     fitness: np.ndarray = field(init=False)          # [P] float32 (-1000 pending)
@@ -128,6 +144,7 @@ class Population:
     def __post_init__(self):
         if self.B > self.P:
             raise ValueError(f"tournament size B={self.B} > population {self.P}")
+        check_frozen_mode(self.frozen_mode)
         self.rng = np.random.RandomState(self.seed)
         self.frozen = np.zeros((self.L, self.M), np.float32)
         self.fitness = np.full(self.P, FITNESS_PENDING, np.float32)
@@ -156,8 +173,8 @@ class Population:
             busy.update(c)
 
     def expressed(self) -> np.ndarray:
-        """[P, L, M] expressed masks."""
-        return ((self.genotypes > 0.5) | (self.frozen[None] > 0.5)).astype(np.float32)
+        """[P, L, M] expressed masks: genotype | frozen ("or") or the genotypes alone ("available")."""
+        return express(self.genotypes, self.frozen[None], self.frozen_mode)
 
     # -- tournament -------------------------------------------------------------
     def mutate(self, g):

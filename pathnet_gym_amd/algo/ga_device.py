@@ -13,6 +13,10 @@ in the optimizer hipGraph right after the fitness all-reduce (SURVEY.md
 section 2.8 K17/K18, section 7.1 "GA kernels"), with no host round trip, and
 replicated ranks stay identical by construction.
 
+``mutation_kind="down"`` selects the reference's local-shift operator
+(``pathnet.py:32-48``) on the same draw layout, on the host mirror and in the
+kernel alike (``launch_ga_step_ex``, ``mut_kind`` 1).
+
 Tournaments live in C fixed slots (``slots [C, B]``, -1 = empty).  The host
 mirror (``CounterPopulation``) and the device kernel take identical decisions,
 which the GPU tests check generation by generation.
@@ -105,6 +109,47 @@ def counter_mutation_scalar(g: np.ndarray, L: int, M: int, N: int, seed: int, ge
     return g
 
 
+def counter_mutation_down(g: np.ndarray, L: int, M: int, N: int, seed: int, gen: int, path: int) -> np.ndarray:
+    """The local-shift operator (``ga.mutation_down``, pathnet.py:32-48) with counter-based draws (in place,
+    returned).  Same stream layout as counter_mutation: module m of layer l decides with draw 2m and picks its offset
+    with draw 2m+1; inactive modules draw nothing.  An active module moves iff int(U*L*N) <= 1 and then lands
+    4..1 modules lower (randint(-2,2) - 2 is uniform on {-4..-1}: the draw's low two bits), clamped to the layer.  A
+    target is always below the module that moved, so the walk never meets it again."""
+    ka = L * N
+    ll, mm = np.meshgrid(np.arange(L, dtype=np.uint64), np.arange(M, dtype=np.uint64), indexing="ij")
+    h0 = ga_rand_np(seed, gen, path, ll, 2 * mm).tolist()
+    h1 = ga_rand_np(seed, gen, path, ll, 2 * mm + 1).tolist()
+    for l in range(L):
+        row0, row1 = h0[l], h1[l]
+        for m in range(M):
+            if g[l, m] == 1 and (row0[m] >> 8) * ka < (1 << 25):
+                g[l, m] = 0
+                g[l, min(max(m - 4 + (row1[m] & 3), 0), M - 1)] = 1
+    return g
+
+
+def counter_mutation_down_scalar(g: np.ndarray, L: int, M: int, N: int, seed: int, gen: int, path: int) -> np.ndarray:
+    """The scalar form of counter_mutation_down (the oracle its vectorised draws are tested against)."""
+    ka = L * N
+    for l in range(L):
+        for m in range(M):
+            if g[l, m] != 1:
+                continue
+            h0 = ga_rand(seed, gen, path, l, 2 * m)
+            u24 = h0 >> 8
+            if u24 * ka < (1 << 25):
+                h1 = ga_rand(seed, gen, path, l, 2 * m + 1)
+                off = -4 + (h1 & 3)
+                g[l, m] = 0
+                g[l, min(max(m + off, 0), M - 1)] = 1
+    return g
+
+
+# GAConfig.mutation -> the mut_kind argument of launch_ga_step_ex (csrc/ga.hip)
+MUT_KINDS = {"ref": 0, "down": 1}
+_MUTATE = {"ref": counter_mutation, "down": counter_mutation_down}
+
+
 def draw_slot(seed: int, key_gen: int, slot: int, P: int, B: int, busy: np.ndarray) -> List[int]:
     """B distinct non-busy path indices (marks them busy); [] if fewer than B are free."""
     if int((~busy).sum()) < B:
@@ -129,7 +174,13 @@ def draw_slot(seed: int, key_gen: int, slot: int, P: int, B: int, busy: np.ndarr
 class CounterPopulation(Population):
     """Population whose tournaments/mutations are the counter-based device GA (host mirror)."""
 
+    def _mutate_fn(self):
+        if self.mutation_kind not in _MUTATE:
+            raise ValueError(f"mutation_kind {self.mutation_kind!r}: the counter GA has {sorted(_MUTATE)}")
+        return _MUTATE[self.mutation_kind]
+
     def __post_init__(self):
+        self._mutate_fn()
         self.seed32 = (self.seed * 2654435761) & M32
         self.draw_round = 0
         super().__post_init__()
@@ -155,6 +206,7 @@ class CounterPopulation(Population):
         self.candidates = [list(map(int, r)) for r in self.slots if r[0] >= 0]
 
     def step(self, fitness: np.ndarray, global_step: int = 0) -> List[TournamentEvent]:
+        mutate = self._mutate_fn()
         self.fitness[:] = fitness
         C = self.concurrent
         ready = np.zeros(C, bool)
@@ -182,7 +234,7 @@ class CounterPopulation(Population):
             for i in cand:
                 if i != w:
                     g = self.genotypes[w].copy()
-                    self.genotypes[i] = counter_mutation(g, self.L, self.M, self.N, self.seed32, gen, int(i))
+                    self.genotypes[i] = mutate(g, self.L, self.M, self.N, self.seed32, gen, int(i))
             self.generation += 1
             self.history.append(ev)
             events.append(ev)

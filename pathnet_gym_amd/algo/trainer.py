@@ -38,7 +38,7 @@ from ..runtime.guard import NonFiniteGuard, Watchdog
 from ..utils.metrics import MetricsLogger
 from ..utils.tracing import PhaseTracer, performance_line
 from .a2c_math import a2c_loss, nstep_returns, sample_actions_keyed
-from .ga import Population
+from .ga import Population, check_frozen_mode
 from .optim import RMSPropTF, anneal_lr
 
 
@@ -113,7 +113,8 @@ class PathNetTrainer:
             from .ga_device import CounterPopulation
             pop_cls = CounterPopulation      # host mirror of the device GA (identical decisions)
         self.pop = pop_cls(self.P_total, net.L, net.M, net.N, cfg.ga.B, seed=cfg.ga.seed,
-                           mutation_kind=cfg.ga.mutation, concurrent=cfg.ga.concurrent_tournaments)
+                           mutation_kind=cfg.ga.mutation, concurrent=cfg.ga.concurrent_tournaments,
+                           frozen_mode=check_frozen_mode(getattr(cfg.ga, "frozen_mode", "or")))
         self.model = ACPathNet(net, self.P, self.device, self.backend, seed=cfg.seed,
                                compute_dtype=self.compute_dtype, deterministic=cfg.deterministic)
         a2c = cfg.a2c
@@ -219,7 +220,7 @@ class PathNetTrainer:
         """Freeze the last winner and re-init every other parameter (doom_pathnet.py:274-293)."""
         self.flush()
         winner = self.pop.best()
-        # the path that solved this task, as expressed (its genotype OR the earlier frozen modules)
+        # the path that solved this task, as expressed (its genotype, in "or" mode with the earlier frozen modules)
         self.task_paths[self.task_idx] = self.pop.expressed()[winner].copy()
         frozen = self.pop.freeze(winner, union=self.cfg.ga.freeze_union)
         if self.cfg.net.per_task_heads:

@@ -84,6 +84,8 @@ def build_parser():
         p.add_argument("--mutation", default=None, choices=["ref", "down"])
         p.add_argument("--concurrent_tournaments", type=int, default=None)
         p.add_argument("--freeze_union", type=int, default=None)
+        p.add_argument("--frozen_mode", default=None, choices=["or", "available"],
+                       help="or: frozen modules always expressed (reference RL semantics); available: selectable by later paths")
         p.add_argument("--gray", default=None, choices=["rgb", "bgr"])
         p.add_argument("--frameskip", type=int, default=None)
         p.add_argument("--ga_sync", default=None, choices=["fused", "gather_bcast"])
@@ -214,6 +216,8 @@ def config_from_args(a):
         cfg.ga.concurrent_tournaments = a.concurrent_tournaments
     if a.freeze_union is not None:
         cfg.ga.freeze_union = bool(a.freeze_union)
+    if getattr(a, "frozen_mode", None) is not None:
+        cfg.ga.frozen_mode = a.frozen_mode
     if getattr(a, "no_graph", False):
         cfg.use_graph = False
     if getattr(a, "compute_dtype", None):

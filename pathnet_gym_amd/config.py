@@ -174,6 +174,9 @@ class GAConfig:
     freeze_union: bool = True           # keep union of frozen paths across tasks (paper); False = ref quirk
     backend: str = "host"               # "host": reference MT19937 GA | "device": counter-hash GA kernel in the graph
     seed: int = 1                       # doom_pathnet.py:104 tf.set_random_seed(1)
+    # frozen modules in later tasks: "or" = ORed into every path (doom_pathnet.py:216-221,261-266) | "available" =
+    # used only by the paths whose genotype selects them (the PathNet paper); never trained either way
+    frozen_mode: str = "or"
 
     def window_for(self, envs_per_path: int) -> int:
         """Episodes a path must finish before it can enter a tournament (0 = reference 'last episode')."""

@@ -100,6 +100,9 @@ _SIGS = {
     "fast_conv_set_f16_fwd": [c_int],
     "launch_ga_step": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_uint, P, P],
     "launch_ga_compact": [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
+    # the same two with the mutation operator (0 ref | 1 down) / the frozen rule (1 OR | 0 available) as an argument
+    "launch_ga_step_ex": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_uint, c_int, P, P],
+    "launch_ga_compact_ex": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
     "launch_typed_fc_fwd": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],
     "launch_typed_fc_dgrad": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],
     "launch_typed_fc_wgrad": [P, P, c_int, c_long, c_long, c_int, c_int, c_int, P, P, c_int, P, P, P],

@@ -29,6 +29,8 @@ from typing import Optional
 import numpy as np
 import torch
 
+from ..algo.ga import FROZEN_MODES
+from ..algo.ga_device import MUT_KINDS
 from ..ops import _lib
 from ..ops import envs as henv
 
@@ -615,7 +617,12 @@ class HipEngine:
     # -- device GA (GAConfig.backend == "device"; algo/ga_device.py mirrors it on the host) --------
     def enable_device_ga(self, pop, comm, p_off: int):
         dev = self.device
+        if pop.mutation_kind not in MUT_KINDS:
+            raise ValueError(f"device GA: mutation {pop.mutation_kind!r}, expected one of {sorted(MUT_KINDS)}")
+        if pop.frozen_mode not in FROZEN_MODES:
+            raise ValueError(f"device GA: frozen_mode {pop.frozen_mode!r}, expected one of {FROZEN_MODES}")
         self.ga_dev = dict(
+            mut_kind=MUT_KINDS[pop.mutation_kind], frozen_or=int(pop.frozen_mode == "or"),
             geno=torch.zeros(pop.P, pop.L, pop.M, dtype=torch.uint8, device=dev),
             frozen=torch.zeros(pop.L, pop.M, dtype=torch.uint8, device=dev),
             slots=torch.full((pop.concurrent, pop.B), -1, dtype=torch.int32, device=dev),
@@ -646,12 +653,13 @@ class HipEngine:
         hp = self.hip
         m = self.model
         st = _lib.stream()
-        _lib.call("launch_ga_step", g["geno"].data_ptr(), g["fit"].data_ptr(), g["slots"].data_ptr(),
+        # the mutation operator and the frozen rule are fixed for the trainer's lifetime: constants of the captured graph
+        _lib.call("launch_ga_step_ex", g["geno"].data_ptr(), g["fit"].data_ptr(), g["slots"].data_ptr(),
                   g["gen"].data_ptr(), g["events"].data_ptr(), pop.P, pop.L, pop.M, pop.N, pop.B, pop.concurrent,
-                  pop.seed32, g["reset"].data_ptr(), st)
-        _lib.call("launch_ga_compact", g["geno"].data_ptr(), g["frozen"].data_ptr(), g["p_off"], self.P, pop.L,
-                  pop.M, m.mask.data_ptr(), m.act_idx.data_ptr(), m.act_cnt.data_ptr(), hp.inv_path.data_ptr(),
-                  hp.inv_slot.data_ptr(), hp.inv_cnt.data_ptr(), st)
+                  pop.seed32, g["mut_kind"], g["reset"].data_ptr(), st)
+        _lib.call("launch_ga_compact_ex", g["geno"].data_ptr(), g["frozen"].data_ptr(), g["p_off"], self.P, pop.L,
+                  pop.M, g["frozen_or"], m.mask.data_ptr(), m.act_idx.data_ptr(), m.act_cnt.data_ptr(),
+                  hp.inv_path.data_ptr(), hp.inv_slot.data_ptr(), hp.inv_cnt.data_ptr(), st)
         _lib.call("launch_active_union", g["geno"].data_ptr(), g["frozen"].data_ptr(), pop.P, pop.L, pop.M,
                   g["union"].data_ptr(), st)
         # local fitness <- the GA's view; ONLY the candidates of tournaments that just fired restart their

@@ -45,6 +45,7 @@ def build_cfg(args, tasks):
     cfg.paths, cfg.envs_per_path, cfg.a2c.t_max = args.paths, args.envs, args.tmax
     cfg.ga.backend = "device"
     cfg.ga.concurrent_tournaments = max(1, args.paths // 16)
+    cfg.ga.frozen_mode = args.frozen_mode
     cfg.steps_per_task = 2 * args.frames          # task switches are driven by this script, never automatic
     cfg.a2c.max_time_step = 2 * args.frames
     cfg.a2c.lr_anneal = "none"
@@ -138,6 +139,8 @@ def main():
                     help="end a task this many frames after its first solving tournament (default: run the budget)")
     ap.add_argument("--control-only", action="store_true",
                     help="only the from-scratch control runs of tasks >= 2 (e.g. in a separate job)")
+    ap.add_argument("--frozen_mode", default="or", choices=["or", "available"],
+                    help="or: frozen modules always expressed (reference RL semantics); available: selectable by later paths")
     ap.add_argument("--out", default="gpurun_out/continual.json")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp32", "fp32x"], help="HIP engine compute dtype")
     ap.add_argument("--ring", action="store_true", help="first layer on the frame ring (the fp32x bench default)")
@@ -196,7 +199,8 @@ def main():
                "stage": stage, "tasks": tasks, "frames_per_task": args.frames_per_task, "n_gpus": 1,
                "config": {"preset": args.preset, "use_lstm": cfg.net.use_lstm, "L": cfg.net.L, "paths": args.paths, "envs_per_path": args.envs, "t_max": args.tmax, "N": args.N,
                           "M": cfg.net.M, "B": cfg.ga.B, "trunk_scale": cfg.net.trunk_scale, "lr": cfg.a2c.lr,
-                          "per_task_heads": True, "freeze_union": cfg.ga.freeze_union, "seed": args.seed,
+                          "per_task_heads": True, "freeze_union": cfg.ga.freeze_union,
+                          "frozen_mode": cfg.ga.frozen_mode, "seed": args.seed,
                           "env_reduction": cfg.a2c.env_reduction, "dtype": tr.compute_dtype if tr else None,
                           "stop_after_solve": args.stop_after_solve},
                "per_task": per_task, "scratch_control": controls, "seconds": round(time.time() - t0, 1)}

@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--frozen_mode", default="or", choices=["or", "available"],
+                    help="or: frozen modules always expressed (reference RL semantics); available: selectable by later paths")
     args = ap.parse_args()
     import torch
     from pathnet_gym_amd import _build
@@ -37,6 +39,7 @@ def main():
     cfg.backend, cfg.compute_dtype, cfg.frame_ring = "hip", "fp32x", True
     cfg.ga.backend = "device"
     cfg.ga.concurrent_tournaments = max(1, args.paths // 16)
+    cfg.ga.frozen_mode = args.frozen_mode
     tr = PathNetTrainer(cfg, device=ctx.device, ctx=ctx)
 
     def windows():
@@ -58,14 +61,21 @@ def main():
                 "plans": int(getattr(tr.comm, "plans", 0))}
 
     rec = {"paths": args.paths, "envs": args.envs, "world": ctx.world, "forced_group": bool(ctx.enabled),
-           "backend": ctx.backend}
+           "backend": ctx.backend, "frozen_mode": args.frozen_mode}
+
+    def width():
+        """Mean number of modules a path expresses per layer (what the per-path kernels run)."""
+        return round(float(tr.pop.expressed().sum(2).mean()), 3)
+
     rec["task1_static"] = windows()
     tr.end_task()
     tr._start_task(1)
     rec["frozen_modules"] = int((tr.pop.frozen > 0.5).sum())
+    rec["task2_width_start"] = width()
     rec["task2_static"] = windows()
     tr.static_plan_min_density = 1.01         # the exact plan: only the modules the population expresses
     rec["task2_exact"] = windows()
+    rec["task2_width_end"] = width()
     if ctx.is_main:
         print(json.dumps(rec), flush=True)
     ctx.destroy()
