@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(
 
 // ---------------------------------------------------------------------------
 // backward pointwise: one thread per (row, unit)
-//   dh = dh_heads + keep_t*dh_rec ; dc = keep_t*dc_rec + dh*so*(1-tanh(c)^2)
+//   dh = dh_heads + (keep_t ? dh_rec : 0) ; dc = (keep_t ? dc_rec : 0) + dh*so*(1-tanh(c)^2)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void lstm_bwd_point_kernel(
     const float* __restrict__ dh_heads, const float* __restrict__ dh_rec, const float* __restrict__ dc_rec,
@@ -102,11 +102,13 @@ __global__ __launch_bounds__(256) void lstm_bwd_point_kernel(
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)B * H) return;
   const int row = (int)(idx / H), u = (int)(idx - (long)row * H);
-  const float kt = (done_t && done_t[row]) ? 0.f : 1.f;
+  // keep_t selects (it does not scale): the recurrent gradient of a row whose episode ended at step t is
+  // never read, so a non-finite value left in that slot cannot reach dz (0 * NaN would)
+  const bool kt = !(done_t && done_t[row]);
   float dh = dh_heads[idx];
   float dc = 0.f;
-  if (dh_rec) dh += kt * dh_rec[idx];
-  if (dc_rec) dc = kt * dc_rec[idx];
+  if (dh_rec && kt) dh += dh_rec[idx];
+  if (dc_rec && kt) dc = dc_rec[idx];
   const float* gr = gates + (long)row * 4 * H;
   const float si = gr[u], tj = gr[H + u], sf = gr[2 * H + u], so = gr[3 * H + u];
   const float c = c_t[idx];
@@ -313,6 +315,7 @@ int launch_lstm_wgrad(const void* xh, const float* dz, float* grad, long k_off, 
 
 int launch_lstm_refresh(const float* flat, long k_off, int F, int H, void* KpT, void* Kb, hipStream_t stream) {
   if (F <= 0 || H <= 0 || k_off < 0) return -22;
+  if (F % 64 != 0 || H % 64 != 0) return -1;     // the tile-major permutation leaves KpT's 4H rows when H % 16 != 0
   const long n = (long)(F + H) * 4 * H;
   lstm_refresh_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(flat, k_off, F, H, (bf16_t*)KpT,
                                                                        (bf16_t*)Kb);

@@ -1078,6 +1078,103 @@ def test_engine_lstm_gradient_matches_oracle(hip_lib):
     budget.check("engine_lstm", errs, 8e-2)
 
 
+@pytest.fixture(scope="module", params=["eager", "graph"])
+def lstm_dones_rollout(hip_lib, request):
+    """The `reference` preset in bf16 (Pong, 3 paths x 16 envs, t_max = 5) with episodes capped at 3 agent steps, a
+    period coprime to t_max, so every rollout has episode ends at interior steps and at its last step.  The per-env
+    step counters (column STEPS of the Pong state tensor) are offset by env % 3 before the first update, so the rows
+    end their episodes at different steps.  "graph": hipGraph capture + replays, the last replay is the one compared.
+    -> the engine's gradient, the oracle's (bf16-emulating trunk, lstm_cell_ref with keep from eng.dones, a2c_loss)
+    and two wrong oracles: keep forced to 1, and dones[t] in place of dones[t-1]."""
+    from pathnet_gym_amd.algo.trainer import PathNetTrainer
+    from pathnet_gym_amd.envs.pong import STEPS
+    from pathnet_gym_amd.models.pathnet import ParamStore, bf16_ste, lstm_cell_ref
+    from pathnet_gym_amd.ops import envs as henv
+    graph = request.param == "graph"
+    cfg = preset("reference")
+    cfg.tasks = ["Pong"]
+    cfg.paths, cfg.envs_per_path, cfg.a2c.t_max = 3, 16, 5
+    cfg.use_graph = graph
+    tr = PathNetTrainer(cfg, device=DEV)
+    eng, env = tr.engine, tr.env
+    assert eng.lstm_hip and not eng.hybrid and eng.hst.dtype == torch.bfloat16 and eng.use_graph == graph
+    env.max_episode_steps = 3
+    if not hasattr(env, "_st32"):
+        henv.pong_sync_to_device(env)
+    env._st32[:, STEPS] += (torch.arange(eng.B, device=DEV) % 3).to(torch.int32)     # in place: the graphs keep it
+    for _ in range(3 if graph else 2):
+        tr.update()
+    tr.flush()
+    torch.cuda.synchronize()
+    assert not graph or eng.g_rollout is not None
+    T, P, E, B, A = eng.T, eng.P, eng.E, eng.B, eng.A
+    ended = eng.dones[T - 1].bool().clone()              # the previous rollout's last step
+    h0, c0 = eng.hst[0].float().clone(), eng.cst[0].clone()
+    # the carry's job: the state entering the rollout is zero where the previous rollout ended an episode
+    assert ended.any() and not ended.all()
+    assert not h0[ended].any() and not c0[ended].any()
+    assert bool((h0[~ended].abs().sum(1) > 0).all()) and bool((c0[~ended].abs().sum(1) > 0).all())
+    eng.rollout_backward()
+    torch.cuda.synchronize()
+    dones = eng.dones.bool()
+    assert dones[:T - 1].any() and dones[T - 1].any()
+    assert len({tuple(r) for r in dones.t().tolist()}) >= 3            # the rows end at different steps
+    a2c = cfg.a2c
+    flat = tr.model.store.flat.detach().clone().requires_grad_(True)
+    st = ParamStore(cfg.net, DEV, flat=flat)
+    k, bb = st.lstm()
+    kq = bf16_ste(k)
+    x = eng.obs_stacks().reshape((T + 1) * B, 160, 120, 4).float() / 255.0
+    mask = tr.model.mask.repeat_interleave(E, 0).repeat(T + 1, 1, 1)
+    feat = trunk_forward_ref(st, x, mask, emulate_bf16=True).view(T + 1, B, -1)
+    R, adv = nstep_returns(eng.rewards, eng.values[:T], eng.dones.bool(), eng.values[T], a2c.gamma,
+                           a2c.gae_lambda, a2c.reward_clip)
+
+    def oracle(keep_of):
+        h, c = h0, c0
+        hs = []
+        for t in range(T + 1):
+            if t > 0:
+                keep = keep_of(t)[:, None]
+                h, c = h * keep, c * keep
+            h, c = lstm_cell_ref(bf16_ste(feat[t]), bf16_ste(h), c, kq, bb)
+            hs.append(h)
+        logits, values = heads_ref(st, bf16_ste(torch.stack(hs)).reshape((T + 1) * B, -1))
+        loss, _, _, _ = a2c_loss(logits[:T * B], values[:T * B], eng.actions[:T].reshape(-1).long(), R.reshape(-1),
+                                 adv.reshape(-1), a2c.entropy_beta, a2c.value_coef,
+                                 torch.full((T * B,), eng.weight, device=DEV))
+        return logits.detach(), torch.autograd.grad(loss, flat, retain_graph=True)[0]
+
+    kf = 1.0 - eng.dones.float()
+    logits, g_ref = oracle(lambda t: kf[t - 1])
+    _, g_keep1 = oracle(lambda t: torch.ones_like(kf[0]))
+    _, g_shift = oracle(lambda t: kf[min(t, T - 1)])       # the bootstrap step (t = T) has no dones[T]: it keeps T-1's
+    return dict(mode=request.param, tr=tr, eng=eng, logits=logits, g_ref=g_ref, g_hip=eng.grad_flat.clone(),
+                g_keep1=g_keep1, g_shift=g_shift)
+
+
+def test_engine_lstm_gradient_with_episode_ends(lstm_dones_rollout):
+    """The bf16 reverse scan with episode ends inside the rollout and at its last step: the done mask on the
+    recurrent gradients (kt), the dh_rec / dc_rec ping-pong, which dones[t] goes to which step, and the carry's
+    reset == autograd over the stored rollout.  Negative controls from the oracle alone: a recurrence that ignores
+    the episode ends, and one that uses dones[t] where dones[t-1] belongs, must both leave the budget this test
+    applies to the LSTM gradient -- a budget that could not see the mask would be of no use."""
+    r = lstm_dones_rollout
+    tr, eng = r["tr"], r["eng"]
+    T, B, A = eng.T, eng.B, eng.A
+    budget.check("engine_lstm_dones_fwd", {"logits": rel(r["logits"][:T * B], eng.logits[:T].reshape(-1, A))}, 3e-2)
+    errs = grad_errors(tr, r["g_hip"], r["g_ref"])
+    print(r["mode"], {k_: round(v, 4) for k_, v in sorted(errs.items(), key=lambda kv: -kv[1])[:8]})
+    assert "lstm" in errs
+    ctrl = {name: grad_errors(tr, r[name], r["g_ref"])["lstm"] for name in ("g_keep1", "g_shift")}
+    print("lstm error of the wrong oracles:", ctrl, "of the engine:", errs["lstm"])
+    budget.check("engine_lstm_dones", errs, 8e-2)
+    rec = budget._load(budget.MEASURED).get("engine_lstm_dones", {}).get("lstm")
+    applied = 8e-2 if rec is None or os.environ.get("PATHNET_RECORD_NUMERICS") else budget.HEADROOM * max(rec, 1e-5)
+    for name, v in ctrl.items():
+        assert v > max(applied, 8e-2), (name, v, applied)
+
+
 @pytest.mark.parametrize("E", [16, 32])
 def test_slab_conv_kernels_match_fast(hip_lib, E):
     """LDS-slab implicit-im2col conv fwd/wgrad == the register-im2col fast kernels (all-active path included)."""
