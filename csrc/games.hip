@@ -410,6 +410,235 @@ struct Centipede {
   }
 };
 
+// --------------------------------------------------------------------------- synthetic Doom scenarios
+// envs/doom_games.py: one physics() call is one Doom tic; a finished episode plays no further tic of its agent
+// step.  LIVING / DEATH_PENALTY / TIMEOUT are the scenario table's values (envs/doom/scenarios.py; the torch class
+// imports them, tests/test_doom_games.py compares them with these).  Per-monster / per-fireball loops run over
+// compile-time bounds and never index the state row with a run-time value, so the row stays in registers.
+struct DoomView {
+  static constexpr int K = 64, Z0 = 32, ZFAR = 96, HORIZON = 80, FH = 50, HUD_Y0 = 186;
+  static constexpr int WALL_Y0 = HORIZON - FH * K / (ZFAR + Z0), WALL_H = 2 * (FH * K / (ZFAR + Z0));
+  static constexpr int NBACK = 3;
+  static DEVI void backdrop(int16_t* r) {
+    rect(r, 0, 0, 0, HORIZON, 160);
+    rect(r, 1, HORIZON, 0, HUD_Y0 - HORIZON, 160);
+    rect(r, 2, WALL_Y0, 0, WALL_H, 160);
+  }
+  // object of world size w x h on the floor at lateral offset dx (screen x centre cx given), depth z
+  static DEVI void object(int16_t* r, int i, int cx, int z, int w, int h, bool visible, int lift = 0) {
+    const int den = z + Z0;
+    const int pw = fdiv(w * K, den), ph = fdiv(h * K, den);
+    const int yb = HORIZON + fdiv(FH * K, den);
+    rect(r, i, yb - ph - lift, cx - fdiv(pw, 2), visible ? ph : 0, pw);
+  }
+  static DEVI int xproj(int dx, int z) { return 80 + fdiv(dx * K, z + Z0); }
+  // side-wall edges at +-room and two far-wall pillars at +-pillar, drawn at x - px: rectangles i .. i + 3
+  static DEVI void strafe_walls(int16_t* r, int i, int px, int room, int pillar) {
+    rect(r, i, WALL_Y0, xproj(-room - px, ZFAR) - 200, WALL_H, 200);
+    rect(r, i + 1, WALL_Y0, xproj(room - px, ZFAR), WALL_H, 200);
+    object(r, i + 2, xproj(-pillar - px, ZFAR), ZFAR, 8, 2 * FH, true);
+    object(r, i + 3, xproj(pillar - px, ZFAR), ZFAR, 8, 2 * FH, true);
+  }
+  // [gun], HUD strip, health bar, [ammo bar]: returns the next free rectangle
+  static DEVI int hud(int16_t* r, int i, int health, int ammo, bool weapon) {
+    if (weapon) rect(r, i++, HUD_Y0 - 20, 74, 20, 12);
+    rect(r, i++, HUD_Y0, 0, 210 - HUD_Y0, 160);
+    rect(r, i++, HUD_Y0 + 4, 8, 6, fdiv(max(health, 0) * 3, 5));
+    if (weapon) rect(r, i++, HUD_Y0 + 14, 8, 6, max(ammo, 0) * 2);
+    return i;
+  }
+};
+
+struct DoomBasic : DoomView {
+  static constexpr int LIVING = -10, TIMEOUT = 350;
+  static constexpr int XMAX = 100, ROOM = 130, SPEED = 4, PILLAR = 50, MON_W = 24, MON_H = 40, MON_HALF = 12;
+  static constexpr int KILL = 101, SHOT = -5, COOLDOWN = 8, AMMO = 50;
+  enum { PX, MX, COOL, TIC, KILLED, AMMOF, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + 4 + 1 + 4;
+  static DEVI void reset(int* s, const Rng& g) {
+    s[PX] = 0;
+    s[MX] = g.rand(20, 2 * XMAX + 1) - XMAX;
+    s[COOL] = 0;
+    s[TIC] = 0;
+    s[AMMOF] = AMMO;
+    s[KILLED] = 0;
+  }
+  static DEVI bool over(const int* s) { return s[KILLED] != 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng&) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[PX] = clampi(s[PX] + SPEED * ((a == 2) - (a == 3)), -XMAX, XMAX);
+    const int cool = max(s[COOL] - 1, 0);
+    const bool fire = a == 1 && cool == 0 && s[AMMOF] > 0;
+    const bool hit = fire && iabs(s[MX] - s[PX]) <= MON_HALF;
+    s[COOL] = fire ? COOLDOWN : cool;
+    s[AMMOF] -= fire;
+    s[KILLED] = hit;
+    return LIVING + (fire ? SHOT : 0) + (hit ? KILL : 0);
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    strafe_walls(r, NBACK, s[PX], ROOM, PILLAR);
+    object(r, NBACK + 4, xproj(s[MX] - s[PX], ZFAR), ZFAR, MON_W, MON_H, s[KILLED] == 0);
+    hud(r, NBACK + 5, 100, s[AMMOF], true);
+  }
+};
+
+struct DoomDefendCenter : DoomView {
+  static constexpr int DEATH_PENALTY = 1, TIMEOUT = 2100;
+  static constexpr int NM = 5, NP = 8, TURN = 3, DMAX = 96, STAGGER = 8, MON_W = 16, MON_H = 40;
+  static constexpr int TOL0 = 6, TOLDIV = 8, COOLDOWN = 8, AMMO = 26, RESPAWN = 16, BITE = 8, DAMAGE = 10, HEALTH = 100;
+  enum { TH, COOL, AMMOF, HEALTHF, TIC, MA, MD = MA + NM, MT = MD + NM, ALIVE = MT + NM, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + NP + NM + 4;
+  static DEVI int spawn_angle(const Rng& g, int k, int tic) { return fmodi(g.rand(30 + k, 256) + tic * 41, 256); }
+  static DEVI int offset(int ang, int th) { return fmodi(ang - th + 128, 256) - 128; }
+  static DEVI void reset(int* s, const Rng& g) {
+    s[TH] = 0;
+    s[COOL] = 0;
+    s[AMMOF] = AMMO;
+    s[HEALTHF] = HEALTH;
+    s[TIC] = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      s[MA + k] = spawn_angle(g, k, 0);
+      s[MD + k] = DMAX - STAGGER * k;
+      s[MT + k] = 0;
+    }
+    s[ALIVE] = (1 << NM) - 1;
+  }
+  static DEVI bool over(const int* s) {
+    return s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT || (s[AMMOF] <= 0 && s[COOL] <= 0);
+  }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = fmodi(s[TH] + TURN * ((a == 2) - (a == 3)), 256);
+    const int cool = max(s[COOL] - 1, 0);
+    const bool fire = a == 1 && cool == 0 && s[AMMOF] > 0;
+    s[COOL] = fire ? COOLDOWN : cool;
+    s[AMMOF] -= fire;
+    int alive = s[ALIVE];
+    // the shot kills the nearest living monster inside its aim tolerance (ties: the lowest index)
+    constexpr int BIG = 1 << 20;
+    int key = BIG;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      const int tol = TOL0 + fdiv(DMAX - s[MD + k], TOLDIV);
+      const bool cand = ((alive >> k) & 1) && iabs(offset(s[MA + k], s[TH])) <= tol;
+      key = min(key, cand ? s[MD + k] * 8 + k : BIG);
+    }
+    const bool kill = fire && key < BIG;
+    int reward = kill;
+    int biting = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      if (kill && (key & 7) == k) {
+        alive &= ~(1 << k);
+        s[MT + k] = RESPAWN;
+      }
+      if ((alive >> k) & 1) {                    // walk inward, bite at distance 0
+        s[MD + k] = max(s[MD + k] - 1, 0);
+        biting += s[MD + k] == 0;
+      }
+    }
+    if (fmodi(s[TIC], BITE) == 0) s[HEALTHF] -= biting * DAMAGE;
+#pragma unroll
+    for (int k = 0; k < NM; ++k)                 // dead slots come back at the rim after RESPAWN tics
+      if (!((alive >> k) & 1)) {
+        s[MT + k] = max(s[MT + k] - 1, 0);
+        if (s[MT + k] == 0) {
+          alive |= 1 << k;
+          s[MD + k] = DMAX;
+          s[MA + k] = spawn_angle(g, k, s[TIC]);
+        }
+      }
+    s[ALIVE] = alive;
+    if (s[HEALTHF] <= 0) reward -= DEATH_PENALTY;
+    return reward;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) object(r, NBACK + k, 80 + fdiv(offset(32 * k, s[TH]) * 5, 2), ZFAR, 8, 2 * FH, true);
+#pragma unroll
+    for (int k = 0; k < NM; ++k)
+      object(r, NBACK + NP + k, 80 + fdiv(offset(s[MA + k], s[TH]) * 5, 2), s[MD + k], MON_W, MON_H,
+             (s[ALIVE] >> k) & 1);
+    hud(r, NBACK + NP + NM, s[HEALTHF], s[AMMOF], true);
+  }
+};
+
+struct DoomTakeCover : DoomView {
+  static constexpr int LIVING = 1, TIMEOUT = 2100;
+  static constexpr int XMAX = 100, ROOM = 130, SPEED = 4, PILLAR = 50, NSH = 6, NF = 6, SH_W = 16, SH_H = 40;
+  static constexpr int GROW = 200, FIRE = 8, U = 16, FSPEED = 8, FB_W = 12, FB_H = 12, FB_LIFT = 25;
+  static constexpr int HIT_W = 12, DAMAGE = 20, HEALTH = 100;
+  enum { PX, HEALTHF, TIC, FX, FZ = FX + NF, FVX = FZ + NF, FACT = FVX + NF, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + 4 + NSH + NF + 2;
+  static DEVI int shooter_x(int j) {           // in the order the shooters appear
+    return j == 0 ? -18 : j == 1 ? 54 : j == 2 ? -90 : j == 3 ? 90 : j == 4 ? -54 : 18;
+  }
+  static DEVI int shooters(const int* s) { return min(1 + fdiv(s[TIC], GROW), NSH); }
+  static DEVI void reset(int* s, const Rng&) {
+    s[PX] = 0;
+    s[HEALTHF] = HEALTH;
+    s[TIC] = 0;
+    s[FACT] = 0;
+  }
+  static DEVI bool over(const int* s) { return s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[PX] = clampi(s[PX] + SPEED * ((a == 1) - (a == 2)), -XMAX, XMAX);
+    int act = s[FACT], hits = 0;
+#pragma unroll
+    for (int k = 0; k < NF; ++k)                 // fireballs in flight
+      if ((act >> k) & 1) {
+        s[FZ + k] -= FSPEED;
+        s[FX + k] += s[FVX + k];
+        if (s[FZ + k] <= 0) {
+          hits += iabs(fdiv(s[FX + k], U) - s[PX]) <= HIT_W;
+          act &= ~(1 << k);
+        }
+      }
+    int idle = NF;                               // the lowest idle slot after the arrivals
+#pragma unroll
+    for (int k = NF - 1; k >= 0; --k)
+      if (!((act >> k) & 1)) idle = k;
+    s[HEALTHF] -= DAMAGE * hits;
+    // thrown at where the player stands now (selects on the values: a branch per slot made the compiler pick the
+    // slot by address, which put the fireball fields in scratch)
+    const bool launch = fmodi(s[TIC], FIRE) == 0 && idle < NF;
+    const int sx = shooter_x(fmodi(g.rand(40, NSH) + fdiv(s[TIC], FIRE), shooters(s)));
+    const int vx = fdiv((s[PX] - sx) * U, ZFAR / FSPEED);
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      const bool here = launch && k == idle;
+      s[FX + k] = here ? sx * U : s[FX + k];
+      s[FZ + k] = here ? ZFAR : s[FZ + k];
+      s[FVX + k] = here ? vx : s[FVX + k];
+      act |= (here ? 1 : 0) << k;
+    }
+    s[FACT] = act;
+    return LIVING;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    strafe_walls(r, NBACK, s[PX], ROOM, PILLAR);
+    const int ns = shooters(s);
+#pragma unroll
+    for (int j = 0; j < NSH; ++j)
+      object(r, NBACK + 4 + j, xproj(shooter_x(j) - s[PX], ZFAR), ZFAR, SH_W, SH_H, j < ns);
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      const int z = max(s[FZ + k], 0);
+      object(r, NBACK + 4 + NSH + k, xproj(fdiv(s[FX + k], U) - s[PX], z), z, FB_W, FB_H, (s[FACT] >> k) & 1,
+             fdiv(FB_LIFT * K, z + Z0));
+    }
+    hud(r, NBACK + 4 + NSH + NF, s[HEALTHF], 0, false);
+  }
+};
+
 // --------------------------------------------------------------------------- driver
 // mode 0: agent step (actions), mode 1: reset_where(mask).  One thread per env.
 template <class G>
@@ -464,7 +693,8 @@ static int launch(void* state, const void* actions, const void* mask, int mode, 
 
 }  // namespace games
 
-// game ids: 0 Breakout, 1 SpaceInvaders, 2 Alien, 3 MsPacman, 4 Centipede
+// game ids: 0 Breakout, 1 SpaceInvaders, 2 Alien, 3 MsPacman, 4 Centipede, 5 DoomBasic, 6 DoomDefendCenter,
+// 7 DoomTakeCover
 extern "C" int game_layout(int game, int* ns, int* nrects) {
   using namespace games;
   switch (game) {
@@ -473,6 +703,9 @@ extern "C" int game_layout(int game, int* ns, int* nrects) {
     case 2: *ns = Alien::NS; *nrects = Alien::R; return 0;
     case 3: *ns = MsPacman::NS; *nrects = MsPacman::R; return 0;
     case 4: *ns = Centipede::NS; *nrects = Centipede::R; return 0;
+    case 5: *ns = DoomBasic::NS; *nrects = DoomBasic::R; return 0;
+    case 6: *ns = DoomDefendCenter::NS; *nrects = DoomDefendCenter::R; return 0;
+    case 7: *ns = DoomTakeCover::NS; *nrects = DoomTakeCover::R; return 0;
   }
   return -1;
 }
@@ -487,6 +720,9 @@ extern "C" int launch_game_step(int game, void* state, const void* actions, cons
     case 2: return launch<Alien>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 3: return launch<MsPacman>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 4: return launch<Centipede>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 5: return launch<DoomBasic>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 6: return launch<DoomDefendCenter>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 7: return launch<DoomTakeCover>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
   }
   return -1;
 }

@@ -297,6 +297,16 @@ def preset(name: str) -> TrainConfig:
                            paths=64, envs_per_path=32, net=net, steps_per_task=DEVICE_TASK_STEPS,
                            ga=GAConfig(B=3, fitness="mean"),
                            a2c=A2CConfig(max_time_step=DEVICE_TASK_STEPS))
+    if name in ("doom3", "doom-basic", "doom_basic"):
+        # the synthetic first-person Doom scenarios (envs/doom_games.py): the "pong" network with a 4-way head
+        # (DoomBasic / DoomDefendCenter have 4 actions, DoomTakeCover 3), GA fitness and trunk scale of "atari4"
+        tasks = ["DoomBasic", "DoomDefendCenter", "DoomTakeCover"] if name == "doom3" else ["DoomBasic"]
+        net = PathNetConfig(L=5, M=10, N=4, input_shape=(160, 120, 4),
+                            layers=reference_pixel_layers(5, fc=(256, 256)),
+                            trunk_scale="none", num_actions=4, num_tasks=len(tasks))
+        return TrainConfig(env=tasks[0], tasks=tasks, paths=64, envs_per_path=32, net=net,
+                           steps_per_task=DEVICE_TASK_STEPS, ga=GAConfig(B=3, fitness="mean"),
+                           a2c=A2CConfig(max_time_step=DEVICE_TASK_STEPS))
     if name in ("reference", "ref"):
         # the reference's own default network and experiment: L=4 (3 conv + 1 linear 1408->256), M=10, N=4,
         # BasicLSTMCell(256) (USE_LSTM=True, constants.py:30; game_ac_network.py:303-521), 18-way head

@@ -846,3 +846,6 @@ GAMES = {"Breakout": BreakoutVec, "SpaceInvaders": SpaceInvadersVec, "Alien": Al
 
 def make_game(name: str, **kw) -> PixelGameVec:
     return GAMES[name](**kw)
+
+
+from . import doom_games  # noqa: E402,F401  (adds the synthetic Doom scenarios to GAMES)

@@ -146,13 +146,53 @@ def centipede_expert(env):
     return a
 
 
+def doom_basic_expert(env):
+    """Strafe until the monster is inside the shot's width, then shoot."""
+    d = env.mx - env.px
+    a = torch.ones_like(d)                                                     # ATTACK
+    a = torch.where(d > env.MON_HALF, torch.full_like(a, 2), a)                # MOVE_RIGHT
+    a = torch.where(d < -env.MON_HALF, torch.full_like(a, 3), a)               # MOVE_LEFT
+    return a
+
+
+def doom_defend_center_expert(env):
+    """Turn towards the nearest living monster; shoot once it is inside the aim tolerance."""
+    dist = torch.where(env.alive, env.md, torch.full_like(env.md, 1 << 20))
+    k = dist.argmin(1, keepdim=True)
+    off = env.offsets(env.ma).gather(1, k).squeeze(1)
+    tol = env.tolerance().gather(1, k).squeeze(1)
+    a = torch.ones_like(off)                                                   # ATTACK
+    a = torch.where(off > tol, torch.full_like(a, 2), a)                       # TURN_RIGHT
+    a = torch.where(off < -tol, torch.full_like(a, 3), a)                      # TURN_LEFT
+    return torch.where(env.alive.any(1), a, torch.zeros_like(a))
+
+
+def doom_take_cover_expert(env):
+    """Step out of the predicted arrival x of the fireballs: of staying, strafing right and strafing left, take the
+    one that leaves the fewest fireballs within the hit width when they arrive (the nearest counts most)."""
+    left_tics = torch.div(env.fz + env.FSPEED - 1, env.FSPEED, rounding_mode="floor").clamp(min=0)
+    arrival = torch.div(env.fx + env.fvx * left_tics, env.U, rounding_mode="floor")
+    weight = torch.where(env.fact, 1 << (12 - left_tics.clamp(max=12)), torch.zeros_like(left_tics))
+    costs = []
+    for d in (0, 1, -1):                                                       # NOOP, MOVE_RIGHT, MOVE_LEFT
+        p = (env.px[:, None] + d * env.SPEED * left_tics).clamp(-env.XMAX, env.XMAX)
+        costs.append((weight * ((arrival - p).abs() <= env.HIT_W + env.SPEED)).sum(1))
+    return torch.stack(costs, 1).argmin(1)
+
+
 EXPERTS = {"Pong": pong_expert, "Breakout": breakout_expert, "SpaceInvaders": invaders_expert,
-           "Alien": alien_expert, "MsPacman": alien_expert, "Centipede": centipede_expert}
+           "Alien": alien_expert, "MsPacman": alien_expert, "Centipede": centipede_expert,
+           "DoomBasic": doom_basic_expert, "DoomDefendCenter": doom_defend_center_expert,
+           "DoomTakeCover": doom_take_cover_expert}
 
 
 def play(game: str, policy: str, n: int, episodes: int, max_steps: int, device, seed: int = 7):
+    from pathnet_gym_amd.envs.atari_games import GAMES
     from pathnet_gym_amd.envs.registry import make
-    env = make(game, num_envs=n, device=device, seed=seed, backend="torch")
+    if game in GAMES:              # a game without a record yet is not in the registry: build it directly
+        env = GAMES[game](num_envs=n, device=device, seed=seed, backend="torch")
+    else:
+        env = make(game, num_envs=n, device=device, seed=seed, backend="torch")
     env.reset()
     g = torch.Generator(device="cpu").manual_seed(seed)
     rets = [[] for _ in range(n)]
@@ -179,7 +219,8 @@ def play(game: str, policy: str, n: int, episodes: int, max_steps: int, device, 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--games", default="Pong,Breakout,SpaceInvaders,Alien,MsPacman,Centipede")
+    ap.add_argument("--games", default="Pong,Breakout,SpaceInvaders,Alien,MsPacman,Centipede,"
+                                       "DoomBasic,DoomDefendCenter,DoomTakeCover")
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--max-steps", type=int, default=27000)
@@ -203,6 +244,10 @@ def main():
         doc = {"rule": f"threshold = random + {FRACTION} * (expert - random) (Pong: max with the ALE 18)",
                "source": "scripts/calibrate_thresholds.py", "envs": args.envs, "episodes_per_env": args.episodes,
                "games": res}
+        if os.path.exists(args.out):           # merge: the games that did not run keep their records as they are
+            with open(args.out) as f:
+                old = json.load(f)
+            doc = dict(old, games=dict(old.get("games", {}), **res))
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the on-device Pong env step kernels (packed stack push vs frame ring).
+"""Micro-benchmark of the on-device env step kernels: Pong (packed stack push vs frame ring) and the rectangle
+games' frame-ring step (``game_step`` + ``rects16_ring_push``, timed together and each alone).
 
-    python scripts/env_microbench.py [--envs 2048] [--iters 200]
+    python scripts/env_microbench.py [--envs 2048] [--iters 200] [--games Centipede,DoomBasic,...]
 Prints one JSON line per variant with the mean kernel time (us) measured with HIP events.
 """
 from __future__ import annotations
@@ -21,6 +22,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--games", default="Centipede,DoomBasic,DoomDefendCenter,DoomTakeCover",
+                    help="rectangle games to time on the frame ring (empty: Pong only)")
     args = ap.parse_args()
     from pathnet_gym_amd import _build
     _build.build()
@@ -58,6 +61,27 @@ def main():
         us_r = timeit(lambda: henv.pong_step_ring_into(env, acts, frames, 5, fc[0], fc[1], r, d, e))
         print(json.dumps({"envs": B, "frameskip": fs, "packed_us": round(us_p, 2), "ring_us": round(us_r, 2)}))
     env.frameskip = base_fs
+
+    from pathnet_gym_amd.envs.atari_games import GAMES
+    gen = torch.Generator().manual_seed(1)
+    for name in [x.strip() for x in args.games.split(",") if x.strip()]:
+        g = GAMES[name](B, device=dev, seed=3, backend="hip")
+        g.reset()
+        for _ in range(50):           # a mid-episode state: objects on screen, episodes ending at different steps
+            g.step(torch.randint(0, g.num_actions, (B,), generator=gen).to(dev))
+        a = torch.randint(0, g.num_actions, (B,), generator=gen).to(device=dev, dtype=torch.int32)
+
+        def logic():
+            g._hip_run(a, None, r, d, e)
+
+        def raster():
+            henv.rects16_ring_push(g._rects, g._gray_tab, g._bg_gray, frames, 5, fc[0], fc[1], d, g._tab32)
+
+        us_l, us_r = timeit(logic), timeit(raster)
+        us = timeit(lambda: g.step_ring_into(a, frames, 5, fc[0], fc[1], r, d, e))
+        print(json.dumps({"game": name, "envs": B, "rects": g._rects.shape[1], "state_ints": g._st32.shape[1],
+                          "ring_step_us": round(us, 2), "game_step_us": round(us_l, 2),
+                          "rects16_ring_push_us": round(us_r, 2)}))
 
 
 if __name__ == "__main__":
