@@ -705,7 +705,9 @@ int launch_conv_wgrad(const void* X, int u8in, const float* G, const void* bits,
   if (chunk <= 0 || L <= 0 || M <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || KH <= 0 || KW <= 0 || S <= 0 ||
       Ho <= 0 || Wo <= 0 || K <= 0 || KP <= 0 || P <= 0 || E <= 0 || T <= 0 || bits_rows <= 0 ||
       rows_per_chunk <= 0 || u8in < 0 || w_off < 0 || b_off < 0 || layer < 0) return -22;
-  if (M > MAXM || KP % 32 != 0 || KP > 512 || rows_per_chunk % 32 != 0) return -1;
+  // KP <= 256: a wave owns k-tiles w, w + 4, w + 8, w + 12 of 16 (acc[4][..]), so 16 tiles is all the kernel computes;
+  // (KW * Cin) % 8: 8 consecutive k = (kh, kw, ci) are one vector load, contiguous only inside a kernel row
+  if (M > MAXM || KP % 32 != 0 || KP > 256 || rows_per_chunk % 32 != 0 || (KW * Cin) % 8 != 0) return -1;
   ConvGeomB g{Hin, Win, Cin, KH, KW, S, Ho, Wo, K, KP};
   const long rows = (long)T * E * Ho * Wo;
   dim3 grid((unsigned)((rows + rows_per_chunk - 1) / rows_per_chunk), P);

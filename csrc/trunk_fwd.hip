@@ -444,7 +444,8 @@ int launch_conv_fwd(const void* X, int u8in, void* Y, void* bits, const void* Wc
   if (chunk <= 0 || L <= 0 || M <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || KH <= 0 || KW <= 0 || S <= 0 ||
       Ho <= 0 || Wo <= 0 || K <= 0 || KP <= 0 || P <= 0 || E <= 0 || T <= 0 || bits_rows <= 0 || u8in < 0 ||
       bias_off < 0 || layer < 0 || t0 < 0) return -22;
-  if (M > MAXM || KP % 32 != 0 || (E * Ho * Wo) % 16 != 0) return -1;
+  // (KW * Cin) % 8: the kernel loads 8 consecutive k = (kh, kw, ci) from one address, contiguous only inside a kernel row
+  if (M > MAXM || KP % 32 != 0 || KP > 512 || (E * Ho * Wo) % 16 != 0 || (KW * Cin) % 8 != 0) return -1;
   ConvGeom g{Hin, Win, Cin, KH, KW, S, Ho, Wo, K, KP};
   const long rows = (long)T * E * Ho * Wo;
   dim3 grid((unsigned)((rows + FWD_BM - 1) / FWD_BM), P);

@@ -208,7 +208,12 @@ def trunk_forward_ref(store: ParamStore, x: torch.Tensor, mask: torch.Tensor,
                   kernels' storage precision; fp32 accumulation either way).  A
                   first conv layer (uint8 pixels in the HIP engine) keeps fp16
                   weights there (csrc/conv_fast.hip fp16-offset path), so it is
-                  rounded to fp16 instead.
+                  rounded to fp16 instead.  That holds for the specialised
+                  160x120x4 8x8/s4 kernel only: a first conv layer of any other
+                  geometry runs csrc/trunk_fwd.hip conv_fwd_kernel on the bf16
+                  copy, which this flag does not emulate
+                  (tests/test_trunk_geometry.py compares those layers with the
+                  operand copies the kernels read instead).
     returns [B, feature_dim]
     """
     cfg = store.cfg

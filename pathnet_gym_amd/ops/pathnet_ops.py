@@ -101,7 +101,8 @@ X3_CONV_GEOMS = ((160, 120, 4, 8, 4, True), (39, 29, 8, 4, 2, False), (18, 13, 8
 def x3_unsupported_reason(net) -> Optional[str]:
     """Why the fp32x kernels cannot run PathNetConfig ``net`` (None: they can).  The trainer then runs the fp32 engine
     (csrc/trunk_f32.hip: fp32 operands, at least the accuracy fp32x promises, bit-reproducible, slower) instead of
-    failing -- e.g. for the reference's --kernel_num / --stride_size flags beyond the default 8,4,3 / 4,2,1 trunk."""
+    failing -- e.g. for the reference's --kernel_num / --stride_size flags beyond the default 8,4,3 / 4,2,1 trunk.  A
+    trunk outside that engine's own envelope (geometry_unsupported_reason) is then refused when the model is built."""
     if net.M > 10:
         return f"M={net.M} > 10 modules per layer"
     for l, (spec, (ins, outs, K, cin)) in enumerate(zip(net.layers, net.layer_shapes())):
@@ -114,6 +115,37 @@ def x3_unsupported_reason(net) -> Optional[str]:
     return None
 
 
+# limits of the runtime-geometry trunk kernels (csrc/trunk_fwd.hip, trunk_bwd.hip, trunk_f32.hip)
+MAX_MODULES = 16          # MAXM / F32_MAXM: module slots a workgroup holds
+CONV_FWD_MAX_KP = 512     # conv forward: padded fan-in of one LDS / register weight tile
+CONV_WGRAD_MAX_KP = 256   # conv weight gradient: 4 waves x 4 k-tiles of 16 (F32_WG_NX in fp32)
+
+
+def geometry_unsupported_reason(net, compute_dtype: str = "bf16") -> Optional[str]:
+    """Why no trunk kernel of the bf16 / fp32 engines can run PathNetConfig ``net`` (None: they can), naming the
+    layer.  Pure host arithmetic on the config -- HipPathNet raises it as NotImplementedError at construction, so a
+    trunk built from --kernel_num / --stride_size / another input_shape either runs or is refused before the first
+    update, in every precision (fp32x falls back to fp32 first, x3_unsupported_reason)."""
+    eng = "fp32" if compute_dtype == "fp32" else "bf16"
+    if net.M > MAX_MODULES:
+        return f"M={net.M} > {MAX_MODULES} modules per layer (the {eng} kernels' module slots)"
+    for l, (spec, (ins, outs, K, cin)) in enumerate(zip(net.layers, net.layer_shapes())):
+        if spec.kind != "conv":
+            continue
+        kp = round_up(K, 32)
+        if (spec.kernel * cin) % 8 != 0:
+            # the forward and weight-gradient kernels read 8 consecutive k = (kh, kw, ci) with one vector load,
+            # which stays inside one kernel row of the image only when a row holds a multiple of 8 values
+            return (f"conv layer {l}: a kernel row of KW*Cin = {spec.kernel}*{cin} = {spec.kernel * cin} values is "
+                    f"not a multiple of 8 (the {eng} conv kernels load 8 consecutive k at once)")
+        if kp > CONV_FWD_MAX_KP:
+            return f"conv layer {l}: fan-in K={K} pads to {kp} > {CONV_FWD_MAX_KP} (the {eng} conv forward's limit)"
+        if kp > CONV_WGRAD_MAX_KP:
+            return (f"conv layer {l}: fan-in K={K} pads to {kp} > {CONV_WGRAD_MAX_KP} (the {eng} conv weight "
+                    "gradient's limit)")
+    return None
+
+
 class HipPathNet:
     """Kernel-side view of an ``ACPathNet`` (created by it when backend='hip')."""
 
@@ -123,6 +155,10 @@ class HipPathNet:
     fc_wgrad_gm_min_k = int(os.environ.get("PATHNET_FC_WGRAD_GM_MIN_K", "1024"))
 
     def __init__(self, model):
+        # the geometry envelope first: a config no kernel can run is refused by name, with or without a GPU
+        why = geometry_unsupported_reason(model.cfg, getattr(model, "compute_dtype", "bf16"))
+        if why is not None:
+            raise NotImplementedError(f"HIP trunk: {why}")
         if not torch.cuda.is_available():
             raise RuntimeError("HIP backend requested but no GPU is visible")
         _lib.lib()   # fail loudly if the library is missing
@@ -169,7 +205,7 @@ class HipPathNet:
                 g = LayerGeom("conv", K, round_up(K, 32), cout, Ho * Wo, Ho * Wo * cout, li["offset"], li["chunk"],
                               Hin, Win, Cin, spec.kernel, spec.kernel, spec.stride, Ho, Wo,
                               u8in=(l == 0), in_scale=(1.0 / 255.0 if l == 0 else 1.0))
-                if l == 0 and (Cin * 2) % 8 != 0:
+                if l == 0 and (Cin * spec.kernel) % 8 != 0:
                     raise NotImplementedError("first conv layer needs Cin*KW multiple of 8 bytes")
             else:
                 if spec.module_types is not None and any(t != 1 for t in spec.module_types):
