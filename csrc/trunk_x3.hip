@@ -44,45 +44,10 @@ struct CG {
   static constexpr int HO = (HIN - KH) / S + 1, WO = (WIN - KW) / S + 1, HOWO = HO * WO;
   static constexpr int K = KH * KW * CIN, KP = (K + 31) / 32 * 32, KC = KP / 8;
   static constexpr int IN_ELEMS = HIN * WIN * CIN;
-  static constexpr __host__ __device__ int koff(int kc) {
-    return kc * 8 >= K ? -1
-                       : ((kc * 8 / CIN) / KW * WIN + (kc * 8 / CIN) % KW) * CIN + (kc * 8) % CIN;
-  }
 };
 using C1 = CG<160, 120, 4, 8, 8, 4, true>;
 using C2 = CG<39, 29, 8, 4, 4, 2, false>;
 using C3 = CG<18, 13, 8, 3, 3, 1, false>;
-
-struct RowIt {
-  int r, t, e, pos;
-};
-DEVI void rowit_init(RowIt& it, int r, int E, int howo) {
-  it.r = r;
-  const int s = r / howo;
-  it.pos = r - s * howo;
-  it.t = s / E;
-  it.e = s - it.t * E;
-}
-DEVI void rowit_adv(RowIt& it, int n, int E, int howo) {
-  it.r += n;
-  it.pos += n;
-  while (it.pos >= howo) {
-    it.pos -= howo;
-    if (++it.e == E) { it.e = 0; ++it.t; }
-  }
-}
-DEVI long rowit_sample(const RowIt& it, int p, int E, int PE, int t0) {
-  return (long)(t0 + it.t) * PE + (long)p * E + it.e;
-}
-
-DEVI uint32_t relu_bits_word(const uint64_t (&bal)[4], uint32_t k) {
-  uint32_t w = 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    w |= __builtin_amdgcn_perm((uint32_t)(bal[r] >> 32), (uint32_t)bal[r],
-                               (k << (8 * r)) | (0x0C0C0C0Cu & ~(0xFFu << (8 * r))));
-  return w;
-}
 
 // ---- split-bf16 helpers ----
 typedef __bf16 b2v __attribute__((ext_vector_type(2)));
@@ -164,13 +129,6 @@ DEVI void x3_flag_range(bool bad) {
 // An activation between layers is stored as its fp16 pair in two 16-bit planes, ylo elements apart (22 significant
 // bits; the next layer's forward reads it as is).  The weight gradients meet it with the output gradient, which needs
 // bf16's exponent range, so they convert it to the bf16 pair while staging (x16pair_to_bf16pair).
-DEVI void st_x4(uint16_t* Y, long ylo, long i, float v) {
-  x3_flag_range(x3_oor(v));
-  const uint16_t h = f2h(v);
-  Y[i] = h;
-  Y[i + ylo] = f2h(v - h2f(h));
-}
-DEVI float ld_x4(const uint16_t* Y, long ylo, long i) { return h2f(Y[i]) + h2f(Y[i + ylo]); }
 DEVI void st8_x4(uint16_t* Y, long ylo, const float (&o)[8]) {
   bool bad = false;
 #pragma unroll
@@ -277,7 +235,7 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 // rows-as-A (lane = one channel of four rows) the module-pair sum is one xor-32 exchange, the ReLU-bit byte of a
 // (slot, row) is two lanes' nibbles (no ballot transposes), and each lane writes its four channels of one plane as
 // one 8-byte store (hi plane: q < 2, lo plane: q >= 2) instead of 16 two-byte stores.  Same arithmetic and summation
-// order as the rows-as-A epilogue: bit-identical outputs.
+// order as the rows-as-A epilogue it replaced (bit-identical outputs).
 template <int NC>
 DEVI void conv_epi_sw(const f4v (&acc)[NC], const float* bias_s, int ct0, int cnt, int q, float in_scale,
                       float out_scale, long grow, uint8_t* __restrict__ bits, long bits_rows,
@@ -336,210 +294,10 @@ DEVI void conv_epi_sw(const f4v (&acc)[NC], const float* bias_s, int ct0, int cn
 }
 
 // ===========================================================================
-// first layer forward (uint8 frame stack, 8x8/s4, 160x120x4): fp16 MFMA, exact pixels x (W*2^8) hi/lo pair.
-// grid = (ceil(T*E*HOWO / (NT*128)), P), 256 threads; each wave owns 32-row tiles (2 MFMA row tiles) and walks
-// NT of them with the bf16 engine's one-register-set reload pipeline (conv_fast.hip conv_fwd_fast AFF8 path):
-// a k-step's raw bytes are converted, the same registers are reloaded with the next tile's k-step, then the MFMAs.
-// Wh: [2][M][8][KP] fp16 (hi plane, lo plane at +wlo).  Y: two bf16 planes (lo at +ylo).
-// ===========================================================================
-template <class G, int NT, int LB, bool SW>
-__global__ __launch_bounds__(256, LB) void conv1_fwd_x2(const uint8_t* __restrict__ X, uint16_t* __restrict__ Y,
-                                                      long ylo, uint8_t* __restrict__ bits,
-                                                      const uint16_t* __restrict__ Wh, long wlo,
-                                                      const float* __restrict__ flat, long bias_off, int chunk,
-                                                      const int* __restrict__ act_idx,
-                                                      const int* __restrict__ act_cnt, int layer, int L, int M, int P,
-                                                      int E, int T, int t0, long bits_rows, float in_scale,
-                                                      float out_scale) {
-  static_assert(G::U8 && G::KW * G::CIN == 32 && G::K == G::KP, "affine uint8 first-layer geometry");
-  constexpr int KPs = G::KP + 8;
-  constexpr int NK = G::KP / 32;
-  constexpr int FF_ROWS = NT * 128;
-  __shared__ __attribute__((aligned(16))) uint16_t Ws[2][X3_NCX * 16 * KPs];
-  __shared__ __attribute__((aligned(16))) float bias_s[X3_NCX * 16];
-  __shared__ float wsum_s[X3_NCX * 16];
-  __shared__ int mods[X3_MAXM];
-  const int p = blockIdx.y;
-  const int cnt = act_cnt[p * L + layer];
-  const int nct = (cnt + 1) >> 1;
-  const int tid = threadIdx.x;
-  if (tid < X3_MAXM) mods[tid] = tid < cnt ? act_idx[(p * L + layer) * M + tid] : 0;
-  const int Rtot = T * E * G::HOWO;
-  const int PE = P * E;
-  const int w = tid >> 6, l = tid & 63;
-  const int grp = l >> 4, c16 = l & 15, q = grp, h = c16 >> 3, ch = l & 7;
-  const uint32_t bkey = (uint32_t)(2 * q + h);
-  const bool lin = T == 1;
-  // SW: pixels enter the MFMA as fp16(1024 + v) straight from v_perm (no per-element subtraction); the offset's
-  // contribution 1024 * sum_k W[col][k] is taken out of the bias (wsum_s: the fp32 sum of the staged fp16 pair)
-  static_assert(!SW || G::KC == 32, "SW weight-sum reduction: one column per 32 lanes");
-  const long rowbase = ((long)t0 * PE + (long)p * E) * G::HOWO;
-  const int rfirst = blockIdx.x * FF_ROWS + w * 32;
-  const int npass = nct > X3_NCX ? (nct + X3_NCX - 1) / X3_NCX : 1;
-  RowIt ait[2], eit[2];
-  uint2 araw[2][NK];
-  const uint8_t* asrc[2];
-  // rows past the end read row 0 of the path's first sample: their 16-row halves are never stored
-  auto aff_addr = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const bool va = ait[i].r < Rtot;
-      const int oh = ait[i].pos / G::WO, ow = ait[i].pos - oh * G::WO;
-      const long xb = va ? rowit_sample(ait[i], p, E, PE, t0) * (long)G::IN_ELEMS +
-                               (long)(oh * G::S * G::WIN + ow * G::S) * G::CIN
-                         : rowit_sample(RowIt{0, 0, 0, 0}, p, E, PE, t0) * (long)G::IN_ELEMS;
-      asrc[i] = X + xb + G::koff(grp);
-      rowit_adv(ait[i], 128, E, G::HOWO);
-    }
-  };
-  for (int pass = 0; pass < npass; ++pass) {
-    const int ct0 = pass * X3_NCX;
-    const int ncg = nct == 0 ? 1 : min(X3_NCX, nct - ct0);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      rowit_init(ait[i], rfirst + i * 16 + c16, E, G::HOWO);
-      rowit_init(eit[i], rfirst + i * 16 + (SW ? c16 : 4 * q), E, G::HOWO);
-    }
-    // the first tile's A loads do not depend on LDS: issued before the staging barriers
-    aff_addr();
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int kk = 0; kk < NK; ++kk) araw[i][kk] = *reinterpret_cast<const uint2*>(asrc[i] + kk * G::WIN * G::CIN);
-    __syncthreads();       // mods visible / the previous pass's LDS reads done
-    for (int i = tid; i < ncg * 16 * G::KC; i += 256) {
-      const int col = i / G::KC, kc = i - col * G::KC;
-      const int slot = ct0 * 2 + (col >> 3);
-      s8v vh = {0, 0, 0, 0, 0, 0, 0, 0}, vl = vh;
-      if (slot < cnt) {
-        const long o = ((long)(mods[slot] * 8 + (col & 7))) * G::KP + kc * 8;
-        vh = *reinterpret_cast<const s8v*>(Wh + o);
-        vl = *reinterpret_cast<const s8v*>(Wh + wlo + o);
-      }
-      *reinterpret_cast<s8v*>(Ws[0] + col * KPs + kc * 8) = vh;
-      *reinterpret_cast<s8v*>(Ws[1] + col * KPs + kc * 8) = vl;
-      if constexpr (SW) {
-        const h8v hh = __builtin_bit_cast(h8v, vh), ll = __builtin_bit_cast(h8v, vl);
-        float ws = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ws += (float)hh[j] + (float)ll[j];
-#pragma unroll
-        for (int m = 16; m >= 1; m >>= 1) ws += __shfl_xor(ws, m, 64);
-        if (kc == 0) wsum_s[col] = ws;
-      }
-    }
-    __syncthreads();
-    if (tid < ncg * 16) {
-      const int slot = ct0 * 2 + (tid >> 3);
-      const float b = slot < cnt ? flat[bias_off + (long)mods[slot] * chunk + (tid & 7)] : 0.f;
-      bias_s[tid] = SW ? b - in_scale * 1024.f * wsum_s[tid] : b;
-    }
-    __syncthreads();
-    auto run = [&](auto ncc) {
-      constexpr int NC = decltype(ncc)::value;
-      auto do_tile = [&](const int rbase, auto reload_c) {
-        constexpr bool RELOAD = decltype(reload_c)::value;
-        f4v acc[2][NC];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) acc[i][ct] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (RELOAD) aff_addr();
-#pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-          const s8v a0 = SW ? u8x8_to_f16off(araw[0][kk]) : u8x8_to_f16(araw[0][kk]);
-          const s8v a1 = SW ? u8x8_to_f16off(araw[1][kk]) : u8x8_to_f16(araw[1][kk]);
-          if constexpr (RELOAD) {
-            araw[0][kk] = *reinterpret_cast<const uint2*>(asrc[0] + kk * G::WIN * G::CIN);
-            araw[1][kk] = *reinterpret_cast<const uint2*>(asrc[1] + kk * G::WIN * G::CIN);
-          }
-          const int kc = kk * 4 + grp;
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) {
-            const s8v bh = *reinterpret_cast<const s8v*>(Ws[0] + (ct * 16 + c16) * KPs + kc * 8);
-            const s8v bl = *reinterpret_cast<const s8v*>(Ws[1] + (ct * 16 + c16) * KPs + kc * 8);
-            if constexpr (SW) {
-              acc[0][ct] = mfma16_f16(bl, a0, acc[0][ct]);
-              acc[0][ct] = mfma16_f16(bh, a0, acc[0][ct]);
-              acc[1][ct] = mfma16_f16(bl, a1, acc[1][ct]);
-              acc[1][ct] = mfma16_f16(bh, a1, acc[1][ct]);
-            } else {
-              acc[0][ct] = mfma16_f16(a0, bl, acc[0][ct]);
-              acc[0][ct] = mfma16_f16(a0, bh, acc[0][ct]);
-              acc[1][ct] = mfma16_f16(a1, bl, acc[1][ct]);
-              acc[1][ct] = mfma16_f16(a1, bh, acc[1][ct]);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int r16 = rbase + i * 16;
-          long grow4;
-          if (lin) {
-            grow4 = rowbase + r16 + (SW ? c16 : 4 * q);
-          } else {
-            const RowIt e0 = eit[i];
-            rowit_adv(eit[i], 128, E, G::HOWO);
-            grow4 = rowit_sample(e0, p, E, PE, t0) * G::HOWO + e0.pos;
-          }
-          if (r16 >= Rtot) continue;
-          if constexpr (SW) {
-            conv_epi_sw<NC>(acc[i], bias_s, ct0, cnt, q, in_scale, out_scale, grow4, bits, bits_rows, Y, ylo, pass > 0);
-            continue;
-          }
-          float sum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) {
-            const int slot = (ct0 + ct) * 2 + h;
-            const float bb = bias_s[ct * 16 + c16];
-            uint64_t bal[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float v = acc[i][ct][r] * in_scale + bb;
-              const bool pos = v > 0.f;
-              sum[r] += pos ? v : 0.f;
-              bal[r] = __ballot(pos);
-            }
-            const uint32_t word = relu_bits_word(bal, bkey);
-            if (ch == 0 && slot < cnt) *reinterpret_cast<uint32_t*>(bits + (long)slot * bits_rows + grow4) = word;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sum[r] += __shfl_xor(sum[r], 8, 64);
-          if (h == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const long o = (grow4 + r) * 8 + ch;
-              float y = sum[r] * out_scale;
-              if (pass > 0) y += ld_x4(Y, ylo, o);
-              st_x4(Y, ylo, o, y);
-            }
-          }
-        }
-      };
-      int tile = 0;
-#pragma unroll
-      for (; tile + 1 < NT; ++tile) {
-        const int rbase = rfirst + tile * 128;
-        if (rbase + 128 >= Rtot) break;
-        do_tile(rbase, std::true_type{});
-      }
-      const int rbase = rfirst + tile * 128;
-      if (rbase < Rtot) do_tile(rbase, std::false_type{});
-    };
-    switch (ncg) {
-      case 1: run(std::integral_constant<int, 1>{}); break;
-      case 2: run(std::integral_constant<int, 2>{}); break;
-      default: run(std::integral_constant<int, 3>{}); break;
-    }
-  }
-}
-
-// ===========================================================================
 // first layer forward with the input BAND in LDS: a stage = 8 output rows of one sample (232 positions), whose 36
 // input rows (17 KB of uint8) are copied into LDS with coalesced 16-byte loads while the previous band computes;
-// every pixel fragment is then one conflict-free ds_read_b64 (2 pixels x 4 channels) instead of conv1_fwd_x2's
-// 8-byte global loads (each input byte fetched 4 times through L2, the kernel waiting on them at 2 waves/SIMD).
+// every pixel fragment is then one conflict-free LDS read (2 pixels x 4 channels) instead of 8-byte global loads
+// (each input byte fetched 4 times through L2, the kernel waiting on them at 2 waves/SIMD).
 // Pixels enter as fp16(1024 + v) (v_perm) with the offset folded into the bias, weights (W * 2^8 hi/lo pair) as
 // the MFMA A operand, conv_epi_sw epilogue.  Passes of <= 2 column tiles (4 modules) keep LDS at 2 x 17.3 KB +
 // 33.8 KB so two workgroups share a CU.  grid = (chunks of bands, P).
@@ -573,16 +331,11 @@ DEVI uint4 planes_to_px4(uint4 v) {
 // is frame slot t + max(c, fcv[t][b]) of env b.  A staging chunk is then 4 pixels of each of the 4 planes (four
 // coalesced 4-byte loads) transposed into the packed (pixel, channel) layout at LDS-write time, so the band in LDS
 // and every MFMA operand read are those of the packed-stack kernel.
-// PIPE: the next k-step's pixel and weight fragments are read from LDS while this k-step's MFMAs run (one k-step of
-// fragments ahead instead of a wait on every k-step's reads)
 // F16B: the band is converted to fp16 (1024 + v) ONCE while it is staged (single LDS buffer of 2 x 17.3 KB, one more
 // barrier per band) instead of per MFMA operand read: every pixel of an 8x8/s4 band feeds 4 positions x 2 kernel
 // rows, so the per-read conversion (v_perm per 2 pixels) ran ~4x per pixel
 // SB1: ONE uint8 band buffer (17.3 KB; one more barrier per band, like F16B) so that the workgroup's 51 KB of LDS
 // lets three workgroups share a CU (3 waves / SIMD, <= 168 VGPRs) instead of two
-#ifndef X3_C1_EARLY_BAND
-#define X3_C1_EARLY_BAND 1
-#endif
 // Cost-balanced 1-D schedule over the (path, item) units of P paths x n items, a unit of path p costing
 // cost(act_cnt[p]) (>= 1): called by ONE wave (all 64 lanes), it writes to sched the range of workgroup blockIdx.x of
 // gridDim.x -- from (sched[0], sched[1]) up to, not including, (sched[2], sched[3]) -- the blockIdx.x-th equal share of
@@ -684,7 +437,7 @@ DEVI int c1_npass(int cnt) {
   return nct > 2 ? (nct + 1) / 2 : 1;
 }
 
-template <class G, bool RING = false, bool PIPE = false, bool F16B = false, bool SB1 = false, bool BAL = false>
+template <class G, bool RING = false, bool F16B = false, bool SB1 = false, bool BAL = false>
 __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint8_t* __restrict__ X, uint16_t* __restrict__ Y,
                                                            long ylo, uint8_t* __restrict__ bits,
                                                            const uint16_t* __restrict__ Wh, long wlo,
@@ -699,7 +452,7 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
   constexpr int KPs = G::KP + 8;
   constexpr int NK = G::KP / 32;
   constexpr int NCXT = 2;
-  static_assert(!(F16B && PIPE) && !(SB1 && (F16B || PIPE)), "F16B / SB1: plain k loop, one band buffer");
+  static_assert(!(SB1 && F16B), "F16B / SB1: one band buffer each");
   constexpr bool ONEBUF = F16B || SB1;
   __shared__ __attribute__((aligned(16))) uint8_t Xb[ONEBUF ? 1 : 2][F16B ? 2 * B::BYTES : B::BYTES];
   __shared__ __attribute__((aligned(16))) uint16_t Ws[2][NCXT * 16 * KPs];
@@ -831,7 +584,7 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
     __syncthreads();                                   // mods (and fcs) visible; the previous pass's LDS reads done
     // the first band's loads go out before the weight staging's, so the two global latencies overlap (the staging
     // loop's waits then cover both)
-    if (X3_C1_EARLY_BAND) load_band(b_beg);
+    load_band(b_beg);
     static_assert(G::KC == 32, "weight-sum reduction: one column per 32 lanes");
     for (int i = tid; i < ncg * 16 * G::KC; i += 256) {
       const int col = i / G::KC, kc = i - col * G::KC;
@@ -852,7 +605,6 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
       for (int m = 16; m >= 1; m >>= 1) ws += __shfl_xor(ws, m, 64);
       if (kc == 0) wsum_s[col] = ws;
     }
-    if (!X3_C1_EARLY_BAND) load_band(b_beg);
     __syncthreads();
     if (tid < ncg * 16) {
       const int slot = ct0 * 2 + (tid >> 3);
@@ -885,46 +637,6 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int ct = 0; ct < NC; ++ct) acc[i][ct] = (f4v){0.f, 0.f, 0.f, 0.f};
-        if constexpr (PIPE) {
-          uint2 ra[4];
-          s8v rbh[NC], rbl[NC];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const uint2*>(xb + abase[i]);
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) {
-            rbh[ct] = *reinterpret_cast<const s8v*>(Ws[0] + (ct * 16 + c16) * KPs + grp * 8);
-            rbl[ct] = *reinterpret_cast<const s8v*>(Ws[1] + (ct * 16 + c16) * KPs + grp * 8);
-          }
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            s8v a[4], bh[NC], bl[NC];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = u8x8_to_f16off(ra[i]);
-#pragma unroll
-            for (int ct = 0; ct < NC; ++ct) {
-              bh[ct] = rbh[ct];
-              bl[ct] = rbl[ct];
-            }
-            if (kk + 1 < NK) {                           // (compile-time after unrolling)
-              const int kc = (kk + 1) * 4 + grp;
-#pragma unroll
-              for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const uint2*>(xb + abase[i] + (kk + 1) * B::RB);
-#pragma unroll
-              for (int ct = 0; ct < NC; ++ct) {
-                rbh[ct] = *reinterpret_cast<const s8v*>(Ws[0] + (ct * 16 + c16) * KPs + kc * 8);
-                rbl[ct] = *reinterpret_cast<const s8v*>(Ws[1] + (ct * 16 + c16) * KPs + kc * 8);
-              }
-            }
-#pragma unroll
-            for (int ct = 0; ct < NC; ++ct)
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                acc[i][ct] = mfma16_f16(bl[ct], a[i], acc[i][ct]);
-                acc[i][ct] = mfma16_f16(bh[ct], a[i], acc[i][ct]);
-              }
-            __builtin_amdgcn_sched_barrier(0);         // this k-step's MFMAs + the next one's reads in flight
-          }
-        } else {
 #pragma unroll
         for (int kk = 0; kk < NK; ++kk) {                // k-step kk = kernel row kh
           s8v a[4];
@@ -945,7 +657,6 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
             }
           }
           __builtin_amdgcn_sched_barrier(0);           // one k-step of LDS fragments live at a time
-        }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -971,181 +682,9 @@ __global__ __launch_bounds__(256, SB1 ? 3 : 2) void conv1_fwd_band_x2(const uint
 }
 
 // ===========================================================================
-// forward of the bf16-activation conv layers (39x29x8 4x4/s2, 18x13x8 3x3/s1): A hi/lo planes, B hi/lo in LDS,
-// three MFMAs per (row tile, column tile, k-step).  grid = (ceil(T*E*HOWO / (NT*128)), P).  The next 32-row
-// tile's A fragments (both planes) are loaded while this tile's MFMAs run.
-// ===========================================================================
-template <class G, int NT, int LB, bool DB, bool SW>
-__global__ __launch_bounds__(256, LB) void conv_fwd_x3(const uint16_t* __restrict__ X, long xlo,
-                                                     uint16_t* __restrict__ Y, long ylo, uint8_t* __restrict__ bits,
-                                                     const uint16_t* __restrict__ Wc, long wlo,
-                                                     const float* __restrict__ flat, long bias_off, int chunk,
-                                                     const int* __restrict__ act_idx, const int* __restrict__ act_cnt,
-                                                     int layer, int L, int M, int P, int E, int T, int t0,
-                                                     long bits_rows, float in_scale, float out_scale) {
-  static_assert(!G::U8, "bf16-activation layers");
-  constexpr int KPs = G::KP + 8;
-  constexpr int NK = G::KP / 32;
-  constexpr int FF_ROWS = NT * 128;
-  __shared__ __attribute__((aligned(16))) uint16_t Ws[2][X3_NCX * 16 * KPs];
-  __shared__ __attribute__((aligned(16))) float bias_s[X3_NCX * 16];
-  __shared__ int mods[X3_MAXM];
-  const int p = blockIdx.y;
-  const int cnt = act_cnt[p * L + layer];
-  const int nct = (cnt + 1) >> 1;
-  const int tid = threadIdx.x;
-  if (tid < X3_MAXM) mods[tid] = tid < cnt ? act_idx[(p * L + layer) * M + tid] : 0;
-  const int Rtot = T * E * G::HOWO;
-  const int PE = P * E;
-  const int w = tid >> 6, l = tid & 63;
-  const int grp = l >> 4, c16 = l & 15, q = grp, h = c16 >> 3, ch = l & 7;
-  const uint32_t bkey = (uint32_t)(2 * q + h);
-  const int rfirst = blockIdx.x * FF_ROWS + w * 32;
-  const int npass = nct > X3_NCX ? (nct + X3_NCX - 1) / X3_NCX : 1;
-  for (int pass = 0; pass < npass; ++pass) {
-    const int ct0 = pass * X3_NCX;
-    const int ncg = nct == 0 ? 1 : min(X3_NCX, nct - ct0);
-    __syncthreads();
-    for (int i = tid; i < ncg * 16 * G::KC; i += 256) {
-      const int col = i / G::KC, kc = i - col * G::KC;
-      const int slot = ct0 * 2 + (col >> 3);
-      s8v vh = {0, 0, 0, 0, 0, 0, 0, 0}, vl = vh;
-      if (slot < cnt) {
-        const long o = ((long)(mods[slot] * 8 + (col & 7))) * G::KP + kc * 8;
-        vh = *reinterpret_cast<const s8v*>(Wc + o);
-        vl = *reinterpret_cast<const s8v*>(Wc + wlo + o);
-      }
-      *reinterpret_cast<s8v*>(Ws[0] + col * KPs + kc * 8) = vh;
-      *reinterpret_cast<s8v*>(Ws[1] + col * KPs + kc * 8) = vl;
-    }
-    if (tid < ncg * 16) {
-      const int slot = ct0 * 2 + (tid >> 3);
-      bias_s[tid] = slot < cnt ? flat[bias_off + (long)mods[slot] * chunk + (tid & 7)] : 0.f;
-    }
-    __syncthreads();
-    auto run = [&](auto ncc) {
-      constexpr int NC = decltype(ncc)::value;
-      RowIt ait[2], eit[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        rowit_init(ait[i], rfirst + i * 16 + c16, E, G::HOWO);
-        rowit_init(eit[i], rfirst + i * 16 + (SW ? c16 : 4 * q), E, G::HOWO);
-      }
-      s8v ah[2][NK], al[2][NK];
-      auto load_tile = [&](int rbase) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const bool va = rbase < Rtot && ait[i].r < Rtot;
-          const int oh = ait[i].pos / G::WO, ow = ait[i].pos - oh * G::WO;
-          const long xb = rowit_sample(ait[i], p, E, PE, t0) * (long)G::IN_ELEMS +
-                          (long)(oh * G::S * G::WIN + ow * G::S) * G::CIN;
-          rowit_adv(ait[i], 128, E, G::HOWO);
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            const int off = G::koff(kk * 4 + grp);
-            ah[i][kk] = (s8v){0, 0, 0, 0, 0, 0, 0, 0};
-            al[i][kk] = ah[i][kk];
-            if (va && off >= 0) {
-              ah[i][kk] = *reinterpret_cast<const s8v*>(X + xb + off);
-              al[i][kk] = *reinterpret_cast<const s8v*>(X + xlo + xb + off);
-            }
-          }
-        }
-      };
-      // DB: the next tile's A fragments load into a second register set during this tile's MFMAs (2 waves/SIMD);
-      // otherwise one set, loaded at the top of each tile, and latency is hidden by occupancy (3 waves/SIMD)
-      if constexpr (DB) load_tile(rfirst);
-      for (int tile = 0; tile < NT; ++tile) {
-        const int rbase = rfirst + tile * 128;
-        if (rbase >= Rtot) break;
-        s8v ch_[2][NK], cl_[2][NK];
-        if constexpr (DB) {
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < NK; ++kk) { ch_[i][kk] = ah[i][kk]; cl_[i][kk] = al[i][kk]; }
-          if (tile + 1 < NT) load_tile(rbase + 128);
-        } else {
-          load_tile(rbase);
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < NK; ++kk) { ch_[i][kk] = ah[i][kk]; cl_[i][kk] = al[i][kk]; }
-        }
-        f4v acc[2][NC];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) acc[i][ct] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < NK; ++kk) {
-          const int kc = kk * 4 + grp;
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) {
-            const s8v bh = *reinterpret_cast<const s8v*>(Ws[0] + (ct * 16 + c16) * KPs + kc * 8);
-            const s8v bl = *reinterpret_cast<const s8v*>(Ws[1] + (ct * 16 + c16) * KPs + kc * 8);
-            if constexpr (SW) {
-              acc[0][ct] = mma3h_t(ch_[0][kk], cl_[0][kk], bh, bl, acc[0][ct]);
-              acc[1][ct] = mma3h_t(ch_[1][kk], cl_[1][kk], bh, bl, acc[1][ct]);
-            } else {
-              acc[0][ct] = mma3h(ch_[0][kk], cl_[0][kk], bh, bl, acc[0][ct]);
-              acc[1][ct] = mma3h(ch_[1][kk], cl_[1][kk], bh, bl, acc[1][ct]);
-            }
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int r16 = rbase + i * 16;
-          const RowIt e0 = eit[i];
-          rowit_adv(eit[i], 128, E, G::HOWO);
-          if (r16 >= Rtot) continue;
-          const long grow4 = rowit_sample(e0, p, E, PE, t0) * G::HOWO + e0.pos;
-          if constexpr (SW) {
-            conv_epi_sw<NC>(acc[i], bias_s, ct0, cnt, q, in_scale, out_scale, grow4, bits, bits_rows, Y, ylo, pass > 0);
-            continue;
-          }
-          float sum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int ct = 0; ct < NC; ++ct) {
-            const int slot = (ct0 + ct) * 2 + h;
-            const float bb = bias_s[ct * 16 + c16];
-            uint64_t bal[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float v = acc[i][ct][r] * in_scale + bb;
-              const bool pos = v > 0.f;
-              sum[r] += pos ? v : 0.f;
-              bal[r] = __ballot(pos);
-            }
-            const uint32_t word = relu_bits_word(bal, bkey);
-            if (ch == 0 && slot < cnt) *reinterpret_cast<uint32_t*>(bits + (long)slot * bits_rows + grow4) = word;
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sum[r] += __shfl_xor(sum[r], 8, 64);
-          if (h == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const long o = (grow4 + r) * 8 + ch;
-              float y = sum[r] * out_scale;
-              if (pass > 0) y += ld_x4(Y, ylo, o);
-              st_x4(Y, ylo, o, y);
-            }
-          }
-        }
-      }
-    };
-    switch (ncg) {
-      case 1: run(std::integral_constant<int, 1>{}); break;
-      case 2: run(std::integral_constant<int, 2>{}); break;
-      default: run(std::integral_constant<int, 3>{}); break;
-    }
-  }
-}
-
-// ===========================================================================
 // forward of the bf16-activation conv layers, one SAMPLE per stage: the sample's fp16-pair input (39x29x8 or
 // 18x13x8, 36 / 7.5 KB) is staged in LDS once and every im2col fragment is a ds_read_b128 of one pixel's 8 channels
-// at (position offset) + (tap offset), instead of conv_fwd_x3's 16-byte global fragment loads that read each input
+// at (position offset) + (tap offset), instead of 16-byte global im2col fragment loads that read each input
 // element KH*KW/S^2 times through L2.  Weights as the MFMA A operand (conv_epi_sw epilogue, rows past the
 // sample's positions masked).  Next sample's tile in registers while this one computes.  grid = (chunks, P).
 // ===========================================================================
@@ -1329,7 +868,7 @@ DEVI void conv_fwd_tile_body(const uint16_t* __restrict__ X, long xlo, uint16_t*
   }
 }
 
-template <class G, bool PAIR = false>
+template <class G, bool PAIR>
 __global__ __launch_bounds__(256, 2) void conv_fwd_tile_x3(const uint16_t* __restrict__ X, long xlo,
                                                           uint16_t* __restrict__ Y, long ylo,
                                                           uint8_t* __restrict__ bits, const uint16_t* __restrict__ Wc,
@@ -1349,7 +888,7 @@ __global__ __launch_bounds__(256, 2) void conv_fwd_tile_x3(const uint16_t* __res
 // its samples (writing Y1 and its ReLU bits as the conv2 kernel does), then -- the same samples, so no other workgroup
 // is involved -- layer + 1 reading those Y1 rows back (L2-hot), into Y2; the barrier between the phases orders the
 // workgroup's own global stores and loads.  Same arithmetic as the two launches (bit-identical).
-template <class G1, class G2, bool PAIR1>
+template <class G1, class G2>
 __global__ __launch_bounds__(256, 2) void conv23_fwd_tile_x3(const uint16_t* __restrict__ X, long xlo,
                                                             uint16_t* __restrict__ Y1, long y1lo,
                                                             uint8_t* __restrict__ bits1, long bits_rows1,
@@ -1367,7 +906,7 @@ __global__ __launch_bounds__(256, 2) void conv23_fwd_tile_x3(const uint16_t* __r
   __shared__ __attribute__((aligned(16))) uint16_t lds[(B1 > B2 ? B1 : B2) / 2];
   __shared__ __attribute__((aligned(16))) float bias_s[2 * 16];
   __shared__ int mods[X3_MAXM];
-  conv_fwd_tile_body<G1, PAIR1>(X, xlo, Y1, y1lo, bits1, Wc1, w1lo, flat, bias1_off, chunk1, act_idx, act_cnt, layer, L,
+  conv_fwd_tile_body<G1, true>(X, xlo, Y1, y1lo, bits1, Wc1, w1lo, flat, bias1_off, chunk1, act_idx, act_cnt, layer, L,
                                 M, P, E, T, t0, bits_rows1, samples_per_wg, in_scale, out_scale1, lds, bias_s, mods);
   __syncthreads();     // the workgroup's Y1 stores are visible to its own waves (workgroup-scope fences; a device-scope
                        // __threadfence here wrote back L2 per workgroup: 85 vs 43 us per step at 64 paths)
@@ -1479,10 +1018,11 @@ __global__ __launch_bounds__(256, NCXP <= 2 ? 3 : 2) void conv_wgrad_slab_x3(con
   for (int ks = 0; ks < SB::KS; ++ks)
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
-      // position of k-slot (grp, hf, q) of k-step ks.  pmap 1: lanes 0-31 of one transposed read take 8 consecutive
-      // positions (64 consecutive dwords of the slab: every bank once); pmap 0 (round 4): positions p and p + 8,
-      // 64 dwords apart, two lanes per bank on every read.  The B reads below use the same map, so the MFMA sums
-      // the same 32 products per k-step in another slot order.
+      // position of k-slot (grp, hf, q) of k-step ks.  pmap 1 (what every launch passes): lanes 0-31 of one
+      // transposed read take 8 consecutive positions (64 consecutive dwords of the slab: every bank once); pmap 0
+      // (round 4): positions p and p + 8, 64 dwords apart, two lanes per bank on every read.  The B reads below use
+      // the same map, so the MFMA sums the same 32 products per k-step in another slot order.  The map stays a
+      // runtime argument: folded to the constant, the first-layer instantiations take 1 to 4 more VGPRs.
       int rho = ks * 32 + (pmap ? 16 * hf + 4 * grp : 8 * grp + 4 * hf) + q;
       if (rho >= SB::NPOS) rho = 0;                     // padded position: its G row is zero
       const int ob = rho / G::WO, ow = rho - ob * G::WO;
@@ -1782,200 +1322,8 @@ __global__ __launch_bounds__(256, NCXP <= 2 ? 3 : 2) void conv_wgrad_slab_x3(con
 }
 
 // ===========================================================================
-// weight gradient of the 18x13x8 3x3/s1 layer (KW*CIN = 24: no slab): 512 threads, 32-row stages of im2col rows
-// (hi and lo planes) + masked, split G in double-buffered LDS, one register set of next-stage loads in flight.
-// grid = (chunks, P) (conv_fast.hip conv_wgrad_fast is the bf16 form).
-// ===========================================================================
-#define X3_WG_RB 32
-template <class G>
-__global__ __launch_bounds__(512, 2) void conv_wgrad_x3(const bf16_t* __restrict__ X, long xlo,
-                                                       const float* __restrict__ Gr, const uint8_t* __restrict__ bits,
-                                                       float* __restrict__ grad, long w_off, long b_off, int chunk,
-                                                       const int* __restrict__ act_idx,
-                                                       const int* __restrict__ act_cnt, int layer, int L, int M, int P,
-                                                       int E, int T, long bits_rows, int rows_per_chunk,
-                                                       float in_scale, float g_scale, const float* __restrict__ gamax,
-                                                       long long* __restrict__ fx) {
-  static_assert(!G::U8 && G::HOWO > X3_WG_RB, "bf16 input; one row wrap per stage");
-  constexpr int XS = G::KP + 8;
-  constexpr int GS = X3_NCX * 16 + 8;
-  constexpr int NMT = G::KP / 16;
-  constexpr int NW = 8;
-  constexpr int MPW = (NMT + NW - 1) / NW;
-  constexpr int XIT = (X3_WG_RB * G::KC + 511) / 512;
-  __shared__ __attribute__((aligned(16))) bf16_t Xs[2][2][X3_WG_RB * XS];
-  __shared__ __attribute__((aligned(16))) bf16_t Gs[2][2][X3_WG_RB * GS];
-  __shared__ unsigned long long dbq[X3_NCT * 16];       // det: int64 fixed point; else the float view
-  float* const dbias = reinterpret_cast<float*>(dbq);
-  __shared__ int mods[X3_MAXM];
-  const int p = blockIdx.y;
-  const int cnt = act_cnt[p * L + layer];
-  if (cnt == 0) return;
-  const int nct = (cnt + 1) >> 1;
-  const int tid = threadIdx.x;
-  if (tid < X3_MAXM) mods[tid] = tid < cnt ? act_idx[(p * L + layer) * M + tid] : 0;
-  if (tid < X3_NCT * 16) dbq[tid] = 0ull;
-  const int Rtot = T * E * G::HOWO;
-  const int PE = P * E;
-  const int r_begin = blockIdx.x * rows_per_chunk;
-  const int r_end = min(Rtot, r_begin + rows_per_chunk);
-  const int w = tid >> 6, l = tid & 63;
-  const int grp = l >> 4, i16 = l & 15, q = i16 >> 2, pp = i16 & 3;
-  const int grow = tid >> 3, gsl = tid & 7;       // G staging role (threads < 256): row, slot of the pass
-  const int npass = (nct + X3_NCX - 1) / X3_NCX;
-  const float gs = g16_scale(gamax), ginv = 1.0f / gs;   // G16
-  int xkoff[XIT];
-#pragma unroll
-  for (int j = 0; j < XIT; ++j) {
-    const int it = tid + 512 * j;
-    xkoff[j] = it < X3_WG_RB * G::KC ? G::koff(it % G::KC) : -1;
-  }
-  auto run = [&](auto ncc, const int ct0) {
-    constexpr int NC = decltype(ncc)::value;
-    const bool gact = tid < 256 && gsl < 2 * NC && 2 * ct0 + gsl < cnt;
-    float bpart[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    f4v acc[MPW][NC];
-#pragma unroll
-    for (int a = 0; a < MPW; ++a)
-#pragma unroll
-      for (int b = 0; b < NC; ++b) acc[a][b] = {0.f, 0.f, 0.f, 0.f};
-    RowIt xit[XIT], git;
-#pragma unroll
-    for (int j = 0; j < XIT; ++j) rowit_init(xit[j], r_begin + (tid + 512 * j) / G::KC, E, G::HOWO);
-    rowit_init(git, r_begin + grow, E, G::HOWO);
-    s8v xh[XIT], xlr[XIT];
-    bool xv[XIT];
-    float4 g0r, g1r;
-    uint32_t gbr = 0;
-    bool gv = false;
-    auto load_stage = [&]() {
-#pragma unroll
-      for (int j = 0; j < XIT; ++j) {
-        xv[j] = xkoff[j] >= 0 && xit[j].r < r_end;
-        if (xv[j]) {
-          const int oh = xit[j].pos / G::WO, ow = xit[j].pos - oh * G::WO;
-          const long xo = rowit_sample(xit[j], p, E, PE, 0) * (long)G::IN_ELEMS +
-                          (long)(oh * G::S * G::WIN + ow * G::S) * G::CIN + xkoff[j];
-          xh[j] = *reinterpret_cast<const s8v*>(X + xo);
-          xlr[j] = *reinterpret_cast<const s8v*>(X + xlo + xo);
-        }
-        rowit_adv(xit[j], X3_WG_RB, E, G::HOWO);
-      }
-      gv = gact && git.r < r_end;
-      if (gv) {
-        const long go = rowit_sample(git, p, E, PE, 0) * G::HOWO + git.pos;
-        g0r = *reinterpret_cast<const float4*>(Gr + go * 8);
-        g1r = *reinterpret_cast<const float4*>(Gr + go * 8 + 4);
-        gbr = bits[(long)(2 * ct0 + gsl) * bits_rows + go];
-      }
-      rowit_adv(git, X3_WG_RB, E, G::HOWO);
-    };
-    auto write_stage = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < XIT; ++j) {
-        const int it = tid + 512 * j;
-        if (it < X3_WG_RB * G::KC) {
-          const int row = it / G::KC, kc = it - row * G::KC;
-          s8v bh = {0, 0, 0, 0, 0, 0, 0, 0}, bl = bh;
-          if (xv[j]) {                                                // the activation's fp16 pair as is
-            bh = xh[j];
-            bl = xlr[j];
-          }
-          *reinterpret_cast<s8v*>(&Xs[buf][0][row * XS + kc * 8]) = bh;
-          *reinterpret_cast<s8v*>(&Xs[buf][1][row * XS + kc * 8]) = bl;
-        }
-      }
-      if (tid < 256 && gsl < 2 * NC) {
-        float m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (gv) {
-          const float gg[8] = {g0r.x, g0r.y, g0r.z, g0r.w, g1r.x, g1r.y, g1r.z, g1r.w};
-          mask8(gg, (uint32_t)gbr, m);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c) bpart[c] += m[c];
-        s8v hi, lo;
-        split8hs(m, gs, hi, lo);
-        *reinterpret_cast<s8v*>(&Gs[buf][0][grow * GS + gsl * 8]) = hi;
-        *reinterpret_cast<s8v*>(&Gs[buf][1][grow * GS + gsl * 8]) = lo;
-      }
-    };
-    auto compute = [&](int buf) {
-      s8v bh[NC], bl[NC];
-#pragma unroll
-      for (int nt = 0; nt < NC; ++nt) {
-        const int o0 = (8 * grp + q) * GS + nt * 16 + 4 * pp, o1 = (8 * grp + 4 + q) * GS + nt * 16 + 4 * pp;
-        bh[nt] = tr8(Gs[buf][0] + o0, Gs[buf][0] + o1);
-        bl[nt] = tr8(Gs[buf][1] + o0, Gs[buf][1] + o1);
-      }
-#pragma unroll
-      for (int mi = 0; mi < MPW; ++mi) {
-        const int mt = w + NW * mi;
-        if (mt < NMT) {
-          const int o0 = (8 * grp + q) * XS + mt * 16 + 4 * pp, o1 = (8 * grp + 4 + q) * XS + mt * 16 + 4 * pp;
-          const s8v ah = tr8(Xs[buf][0] + o0, Xs[buf][0] + o1);
-          const s8v al = tr8(Xs[buf][1] + o0, Xs[buf][1] + o1);
-#pragma unroll
-          for (int nt = 0; nt < NC; ++nt) acc[mi][nt] = mma3h(ah, al, bh[nt], bl[nt], acc[mi][nt]);
-        }
-      }
-    };
-    __syncthreads();
-    if (r_begin < r_end) load_stage();
-    int rb = r_begin, buf = 0;
-    for (; rb + X3_WG_RB < r_end; rb += X3_WG_RB, buf ^= 1) {
-      write_stage(buf);
-      __syncthreads();
-      load_stage();
-      compute(buf);
-    }
-    if (rb < r_end) {
-      write_stage(buf);
-      __syncthreads();
-      compute(buf);
-    }
-    const int h = i16 >> 3, ch = l & 7;
-#pragma unroll
-    for (int mi = 0; mi < MPW; ++mi) {
-      const int mt = w + NW * mi;
-      if (mt < NMT) {
-#pragma unroll
-        for (int nt = 0; nt < NC; ++nt) {
-          const int slot = (ct0 + nt) * 2 + h;
-          if (slot < cnt) {
-            const long base = w_off + (long)mods[slot] * chunk;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int k = mt * 16 + 4 * grp + r;
-              if (k < G::K) gacc(grad, fx, base + (long)k * 8 + ch, acc[mi][nt][r] * (in_scale * g_scale * ginv));
-            }
-          }
-        }
-      }
-    }
-    if (gact) {
-#pragma unroll
-      for (int c = 0; c < 8; ++c) lds_acc(dbias, dbq, (2 * ct0 + gsl) * 8 + c, bpart[c] * g_scale, fx);
-    }
-  };
-  for (int pass = 0; pass < npass; ++pass) {
-    const int ct0 = pass * X3_NCX;
-    switch (min(X3_NCX, nct - ct0)) {
-      case 1: run(std::integral_constant<int, 1>{}, ct0); break;
-      case 2: run(std::integral_constant<int, 2>{}, ct0); break;
-      default: run(std::integral_constant<int, 3>{}, ct0); break;
-    }
-  }
-  __syncthreads();
-  if (tid < cnt * 8) {
-    const long bi = b_off + (long)mods[tid >> 3] * chunk + (tid & 7);
-    if (fx) gacc_q(grad, fx, bi, dbq[tid]);
-    else atomicAdd(&grad[bi], dbias[tid]);
-  }
-}
-
-// ===========================================================================
 // weight gradient of the 18x13x8 3x3/s1 layer, one SAMPLE per stage: the sample's fp16-pair input tile is converted
-// to a bf16 pair ONCE into LDS (1872 elements, instead of 9 im2col copies of each element as in conv_wgrad_x3), and
+// to a bf16 pair ONCE into LDS (1872 elements, instead of 9 im2col copies of each element in staged im2col rows), and
 // the MFMA A operand (im2col^T: k = (kh, kw, ci) x 8 positions) is read straight from the tile with
 // ds_read_b64_tr_b16 -- a lane's address is (position offset) + (tap/channel-chunk offset), both precomputed, so
 // there is no im2col staging at all.  B = the masked, split output gradient of <= 4 slots [192 positions][32].
@@ -4301,10 +3649,6 @@ static bool x3_is(int Hin, int Win, int Cin, int KH, int KW, int S, int u8) {
          (u8 != 0) == G::U8;
 }
 
-static int X3_FWD_NT = 8;      // 32-row tiles per wave in the first-layer forward (4 for the bf16-input layers)
-static int X3_FWD_LB = 2;      // first-layer forward: min waves/SIMD (2: 194 VGPRs, no spill; 3: 168 with spills)
-static int X3_FWD_DB = 0;      // bf16-activation conv forward: 1 = double-buffered A registers (2 waves/SIMD),
-                               // 0 = one register set at 3 waves/SIMD (measured: conv3 24.6 -> 16.9 us, conv2 31.1 -> 30.3)
 // slab weight gradient: stages of loads in flight for <= 2 column tiles: 1, 2, or 3 = 2 for the bf16-input layers
 // and 1 for the uint8 first layer (measured, steady-state window: conv1 2.63 (2) -> 2.32 ms (1), conv2 0.50 (2) vs
 // 0.52 ms (1); profiles/r3/kwin_x3_v4*.md)
@@ -4314,10 +3658,6 @@ static int X3_WGRAD_PF = 3;
 // measured (profiles/r4/kwin_c1ncx*.md): 2.28 ms (3 tiles, PF 1) -> 2.02 (2, PF 1) -> 1.94 (2, PF 2; the default: PF 2
 // unless X3_WGRAD_PF == 1)
 static int X3_C1_WG_NCX = 2;
-// conv forward epilogue, bit 0: first layer, bit 1: the bf16-activation layers; set = swapped MFMA orientation
-// (conv_epi_sw; first layer also with the 1024-offset pixels folded into the bias), clear = rows-as-A
-static int X3_FWD_SW = 1;
-static int X3_FC_D = 4;        // fc forward register ring depth (k-steps of hi/lo A and B fragments in flight)
 // fc forward split-K waves per module (1 = fc_fwd_x3, 2 = fc_fwd_ks_x3).  Measured: fc1 66.4 (2) vs 65.1 us (1),
 // fc2 19.7 vs 17.4 (profiles/r3/kwin_x3_v7*.md): more waves on the same weight traffic do not help -- the launch
 // is bound by its L2/MALL traffic, not by load latency
@@ -4326,18 +3666,11 @@ static int X3_FC_KS = 1;
 // fragments), 2 = fc_fwd_mm2_x3 (LDS-staged 128 x 128 tiles), 3 = the same with k split in two workgroups
 // (pre-activation planes; bias, ReLU, bits and the slot sum in fc_slot_sum2_x3)
 static int X3_FC_MMV = 3;
-static int X3_WG3_TILE = 1;
-// conv2/3 forward: 1 = one position tile per weight read, 2 = two (PAIR), 3 = two for the 4x4/s2 layer only (234
-// output positions; the 3x3 layer's 176 leave paired waves idle).  Measured (kwin_x3_v24*.md, v25*.md): 4x4/s2
-// 25.3 us paired vs 26.0-26.2 single (32.5-32.7 in slow runs), 3x3 18.4-18.8 paired vs 15.9-16.2 single
-static int X3_FWD_TILE = 3;
 static int X3_C1_F16B = 1;     // band forward: 1 = the band converted to fp16 once at staging (conv1_fwd_band_x2 F16B;
                                // interleaved A/B: 64 paths 97.1 -> 95.8 us, 8 paths 20.9 -> 20.4)
 static int X3_C1_SB1 = 0;      // band forward (ring): 1 = one band buffer, three workgroups per CU (conv1_fwd_band_x2 SB1)
-static int X3_C1_PIPE = 0;     // band forward: 1 = next k-step's LDS fragments read during this k-step's MFMAs
 static int X3_C1_EMAJ = 1;     // ring slab weight gradient, atomic mode: env-major unit order
 static int X3_C1_BAL = 1;      // ring band forward: cost-balanced 1-D schedule (conv1_fwd_band_x2 BAL)
-static int X3_C1_BAND = 1;     // first-layer forward: 1 = input band in LDS (conv1_fwd_band_x2), 0 = conv1_fwd_x2    // bf16-activation conv forward: 1 = per-sample LDS tile (conv_fwd_tile_x3), 0 = rows
 // input gradients (conv_dgrad_x3, fc_dgrad_gemm_x3): 1 = the weights as THREE fp16 pieces (a fourth MFMA per k-step),
 // exact for fp32 weights: the pair's 2^-23 weight rounding is the same for every row, so it enters a layer's input
 // gradient coherently and the weight gradients below sum it without cancellation (scripts/x3_lstm_diag.py)
@@ -4364,22 +3697,17 @@ static int X3_WG3_TARGET = 256;    // 3x3 tile weight gradient, one round at 1 p
                                    // 512 before: conv3 backward 8 paths 128 -> 117 us, 64 paths 682 -> 676)
 static int X3_FCW_TARGET = 1024;   // narrow fc weight gradient (fc_wgrad_x3): workgroups, via the path split
                                    // (2048 before: fc2 backward 8 paths 114 -> 109 us, 64 paths 330 -> 323)
-// slab weight gradient: k-slot -> position map of the transposed operand reads (conv_wgrad_slab_x3 pmap)
-static int X3_SLAB_PMAP = 1;
 // staged output gradients: 1 = one fp16-pair split per value, masked per slot (mask_pair8); 0 = mask, then split per slot
 static int X3_PRESPLIT = 1;
-static int X3_FH_D = 3;        // fused last fc + heads: k-steps of fragments in flight (fc_heads_fwd_x3 D)
 static int X3_DG_BAL = 1;         // conv_dgrad_x3: cost-balanced 1-D schedule (BAL)
 static int X3_DG_V0 = 0;         // 1 = conv_dgrad_x3v0 (A/B only)
 static int X3_DG_GSPLIT = X3_DG_SPLIT;   // conv_dgrad_x3 grid split (1 = one chunk per workgroup, no balancing)
-static int X3_DG_CAP = 1;          // conv_dgrad_x3: cap at 2 workgroups per CU (dynamic LDS)
 static int X3_DG_TARGET = 512;     // 4x4/s2 input gradient (2048 -> 1536 -> 512: 8 paths 224 -> 214 -> 191 -> 167 us with
                                    // the conv2 weight gradient)
 // module-major fc forward k split: 0 = auto by rows (P*T*E <= 768: 4 parts, else 3), else the fixed part count (2 / 3 / 4 /
 // 8), capped so every part keeps >= 2 k-steps
 static int X3_FC_KS_PARTS = 0;
-static int X3_FCW_KT = 256;     // fc weight gradient from Gm: k tile 256 (Gm re-read 6x at K = 1408) or 128 (11x)
-static int X3_FC_DG_GEMM = 1;  // fc input gradient: 1 = fc_gm_x3 + per-path GEMM (fc_dgrad_gemm_x3), 0 = fc_dgrad_x3    // 3x3/s1 weight gradient: 1 = per-sample LDS tile (conv_wgrad_tile_x3), 0 = im2col rows
+static int X3_FC_DG_GEMM = 1;  // fc input gradient: 1 = fc_gm_x3 + per-path GEMM (fc_dgrad_gemm_x3), 0 = fc_dgrad_x3
 
 // dynamic LDS that caps kernel KERN at CAP resident workgroups per CU.  The latency-bound backward kernels' grids are
 // whole rounds of a given occupancy (X3_DG_TARGET: 512 = 2 per CU); a build whose VGPR count lets a third workgroup
@@ -4417,34 +3745,21 @@ int x3_fx_flush(void* fx, float* grad, long n0, long n1, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-void fast_conv_set_x3_fwd_nt(int nt) { X3_FWD_NT = nt; }
 void fast_conv_set_x3_c1_wg_ncx(int v) { X3_C1_WG_NCX = v == 2 ? 2 : 3; }
-void fast_conv_set_x3_fwd_lb(int lb) { X3_FWD_LB = lb; }
-void fast_conv_set_x3_fwd_db(int db) { X3_FWD_DB = db; }
-void fast_conv_set_x3_fwd_sw(int sw) { X3_FWD_SW = sw; }
-void fast_conv_set_x3_wg3_tile(int t) { X3_WG3_TILE = t; }
 void fast_conv_set_x3_fc_mmv(int v) { X3_FC_MMV = v; }
 void fast_conv_set_x3_fc_dg_gemm(int v) { X3_FC_DG_GEMM = v; }
-void fast_conv_set_x3_fcw_kt(int v) { X3_FCW_KT = v == 128 ? 128 : 256; }
 void fast_conv_set_x3_dg_w3(int v) { X3_DG_W3 = v; }
 void fast_conv_set_x3_dg_fold(int v) { X3_DG_FOLD = v; }
 void fast_conv_set_x3_dg_v0(int v) { X3_DG_V0 = v; }
 void fast_conv_set_x3_dg_bal(int v) { X3_DG_BAL = v; }
 void fast_conv_set_x3_dg_gsplit(int v) { X3_DG_GSPLIT = v == 1 ? 1 : X3_DG_SPLIT; }
-void fast_conv_set_x3_dg_cap(int v) { X3_DG_CAP = v; }
-void fast_conv_set_x3_fwd_tile(int v) { X3_FWD_TILE = v; }
-void fast_conv_set_x3_c1_band(int v) { X3_C1_BAND = v; }
 void fast_conv_set_x3_c1_bal(int v) { X3_C1_BAL = v; }
 void fast_conv_set_x3_c1_emaj(int v) { X3_C1_EMAJ = v; }
 void fast_conv_set_x3_c1_sb1(int v) { X3_C1_SB1 = v; }
-void fast_conv_set_x3_c1_pipe(int v) { X3_C1_PIPE = v; }
 void fast_conv_set_x3_c1_f16b(int v) { X3_C1_F16B = v; }
-void fast_conv_set_x3_fc_d(int d) { X3_FC_D = d; }
 void fast_conv_set_x3_fc_ks(int ks) { X3_FC_KS = ks; }
 void fast_conv_set_x3_wgrad_pf(int pf) { X3_WGRAD_PF = pf; }
-void fast_conv_set_x3_fh_d(int v) { X3_FH_D = v; }
 void fast_conv_set_x3_presplit(int v) { X3_PRESPLIT = v ? 1 : 0; }
-void fast_conv_set_x3_slab_pmap(int v) { X3_SLAB_PMAP = v ? 1 : 0; }
 void fast_conv_set_x3_fc_rt1(int v) { X3_FC_RT1 = v; }
 void fast_conv_set_x3_c1f_target(int v) { X3_C1F_TARGET = v < 1 ? 1 : v; }
 void fast_conv_set_x3_c1f_minb(int v) { X3_C1F_MINB = v < 1 ? 1 : v; }
@@ -4469,73 +3784,34 @@ int x3_conv_fwd(const void* X, long xlo, int u8in, void* Y, long ylo, void* bits
   if (M > 2 * X3_NCT) return 0;
   if (x3_is<C1>(Hin, Win, Cin, KH, KW, S, u8in)) {
     if ((E * C1::HOWO) % 16) return -2;
-    const long rows = (long)T * E * C1::HOWO;
     const float isc = is / (float)(1 << X3_W0_SHIFT);
-    if (X3_C1_BAND) {
-      const long nbands = (long)T * E * BD1<C1>::NB;
-      long bpw = (nbands * P + 511) / 512;                 // ~2 workgroups per CU over the launch
-      if (bpw < 2) bpw = 2;
-      if (X3_C1_F16B)
-        conv1_fwd_band_x2<C1, false, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
-            (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac,
-            layer, L, M, P, E, T, t0, br, (int)bpw, isc, os);
-      else if (X3_C1_PIPE)
-        conv1_fwd_band_x2<C1, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
-            (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac,
-            layer, L, M, P, E, T, t0, br, (int)bpw, isc, os);
-      else
-        conv1_fwd_band_x2<C1><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
-            (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac,
-            layer, L, M, P, E, T, t0, br, (int)bpw, isc, os);
-      const int rc = (int)hipGetLastError();
-      return rc ? -rc : 1;
-    }
-#define C1L(NT_, LB_)                                                                                           \
-  if (X3_FWD_SW & 1) C1LS(NT_, LB_, true); else C1LS(NT_, LB_, false)
-#define C1LS(NT_, LB_, SW_)                                                                                     \
-  conv1_fwd_x2<C1, NT_, LB_, SW_><<<dim3((unsigned)((rows + NT_ * 128 - 1) / (NT_ * 128)), P), 256, 0, st>>>(             \
-      (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac, \
-      layer, L, M, P, E, T, t0, br, isc, os)
-    if (X3_FWD_LB >= 3) {
-      if (X3_FWD_NT >= 8) C1L(8, 3); else C1L(4, 3);
-    } else {
-      if (X3_FWD_NT >= 9) C1L(9, 2); else if (X3_FWD_NT >= 8) C1L(8, 2); else C1L(4, 2);
-    }
-#undef C1L
-#undef C1LS
+    const long nbands = (long)T * E * BD1<C1>::NB;
+    long bpw = (nbands * P + 511) / 512;                 // ~2 workgroups per CU over the launch
+    if (bpw < 2) bpw = 2;
+    if (X3_C1_F16B)
+      conv1_fwd_band_x2<C1, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
+          (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac,
+          layer, L, M, P, E, T, t0, br, (int)bpw, isc, os);
+    else
+      conv1_fwd_band_x2<C1><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
+          (const uint8_t*)X, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac,
+          layer, L, M, P, E, T, t0, br, (int)bpw, isc, os);
     const int rc = (int)hipGetLastError();
     return rc ? -rc : 1;
   }
+  // two position tiles per weight read for the 4x4/s2 layer only (234 output positions; the 3x3 layer's 176 leave
+  // paired waves idle).  Measured (kwin_x3_v24*.md, v25*.md): 4x4/s2 25.3 us paired vs 26.0-26.2 single, 3x3
+  // 18.4-18.8 paired vs 15.9-16.2 single
 #define CFX(Gx)                                                                                                   \
   if (x3_is<Gx>(Hin, Win, Cin, KH, KW, S, u8in)) {                                                                \
     if ((E * Gx::HOWO) % 16) return -2;                                                                           \
-    const long rows = (long)T * E * Gx::HOWO;                                                                     \
-    const dim3 grid((unsigned)((rows + 511) / 512), P);                                                           \
     const float isc = is / (float)(1 << X3_W0_SHIFT);                                                             \
-    if (X3_FWD_TILE) {                                                                                            \
-      const long nsamp = (long)T * E;                                                                             \
-      long spw = (nsamp * P + 511) / 512;                                                                         \
-      if (spw < 2) spw = 2;                                                                                       \
-      if (X3_FWD_TILE == 2 || (X3_FWD_TILE == 3 && Gx::HOWO > 200))                                              \
-        conv_fwd_tile_x3<Gx, true><<<dim3((unsigned)((nsamp + spw - 1) / spw), P), 256, 0, st>>>(                 \
-            (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,   \
-            chunk, ai, ac, layer, L, M, P, E, T, t0, br, (int)spw, isc, os);                                      \
-      else                                                                                                        \
-        conv_fwd_tile_x3<Gx><<<dim3((unsigned)((nsamp + spw - 1) / spw), P), 256, 0, st>>>(                       \
-            (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,   \
-            chunk, ai, ac, layer, L, M, P, E, T, t0, br, (int)spw, isc, os);                                      \
-    } else if (X3_FWD_DB)                                                                                         \
-      conv_fwd_x3<Gx, 4, 2, true, false><<<grid, 256, 0, st>>>(                                                   \
-          (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,     \
-          chunk, ai, ac, layer, L, M, P, E, T, t0, br, isc, os);                                                  \
-    else if (X3_FWD_SW & 2)                                                                                       \
-      conv_fwd_x3<Gx, 4, 3, false, true><<<grid, 256, 0, st>>>(                                                   \
-          (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,     \
-          chunk, ai, ac, layer, L, M, P, E, T, t0, br, isc, os);                                                  \
-    else                                                                                                          \
-      conv_fwd_x3<Gx, 4, 3, false, false><<<grid, 256, 0, st>>>(                                                  \
-          (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,     \
-          chunk, ai, ac, layer, L, M, P, E, T, t0, br, isc, os);                                                  \
+    const long nsamp = (long)T * E;                                                                               \
+    long spw = (nsamp * P + 511) / 512;                                                                           \
+    if (spw < 2) spw = 2;                                                                                         \
+    conv_fwd_tile_x3<Gx, (Gx::HOWO > 200)><<<dim3((unsigned)((nsamp + spw - 1) / spw), P), 256, 0, st>>>(         \
+        (const uint16_t*)X, xlo, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off,     \
+        chunk, ai, ac, layer, L, M, P, E, T, t0, br, (int)spw, isc, os);                                          \
     const int rc = (int)hipGetLastError();                                                                        \
     return rc ? -rc : 1;                                                                                          \
   }
@@ -4560,18 +3836,14 @@ int x3_conv1_ring_fwd(const void* frames, const void* fc, void* Y, long ylo, voi
   if (bpw < X3_C1F_MINB) bpw = X3_C1F_MINB;
   if (bpw > (X3_C1_FWD_FCS - 2) * BD1<C1>::NB) bpw = (X3_C1_FWD_FCS - 2) * BD1<C1>::NB;   // staged fc bytes
   if (X3_C1_BAL && X3_C1_F16B && !X3_C1_SB1)         // the same workgroup count, cost-balanced over the population
-    conv1_fwd_band_x2<C1, true, false, true, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw) * P), 256, 0, st>>>(
+    conv1_fwd_band_x2<C1, true, true, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw) * P), 256, 0, st>>>(
         (const uint8_t*)frames, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai,
         ac, 0, L, M, P, E, T, t0, br, (int)bpw, isc, os, (const uint8_t*)fc, nslots, rbase);
   else if (X3_C1_SB1)
-    conv1_fwd_band_x2<C1, true, false, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
-        (const uint8_t*)frames, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai,
-        ac, 0, L, M, P, E, T, t0, br, (int)bpw, isc, os, (const uint8_t*)fc, nslots, rbase);
-  else if (X3_C1_F16B)
     conv1_fwd_band_x2<C1, true, false, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
         (const uint8_t*)frames, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai,
         ac, 0, L, M, P, E, T, t0, br, (int)bpw, isc, os, (const uint8_t*)fc, nslots, rbase);
-  else if (X3_C1_PIPE)
+  else if (X3_C1_F16B)
     conv1_fwd_band_x2<C1, true, true><<<dim3((unsigned)((nbands + bpw - 1) / bpw), P), 256, 0, st>>>(
         (const uint8_t*)frames, (uint16_t*)Y, ylo, (uint8_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai,
         ac, 0, L, M, P, E, T, t0, br, (int)bpw, isc, os, (const uint8_t*)fc, nslots, rbase);
@@ -4593,23 +3865,17 @@ int x3_conv23_fwd(const void* X, long xlo, void* Y1, long y1lo, void* bits1, lon
   if (!X || !Y1 || !Y2 || !bits1 || !bits2 || !Wc1 || !Wc2 || !flat || !ai || !ac || xlo <= 0 || y1lo <= 0 ||
       y2lo <= 0 || w1lo <= 0 || w2lo <= 0 || br1 <= 0 || br2 <= 0 || chunk1 <= 0 || chunk2 <= 0 || bias1_off < 0 ||
       bias2_off < 0 || layer < 0 || layer + 1 >= L || M <= 0 || P <= 0 || E <= 0 || T <= 0 || t0 < 0) return -22;
-  if (M > 2 * X3_NCT || !X3_FWD_TILE) return 0;
+  if (M > 2 * X3_NCT) return 0;
   if ((E * C2::HOWO) % 16 || (E * C3::HOWO) % 16) return -2;
   const long nsamp = (long)T * E;
   long spw = (nsamp * P + X3_C23_TARGET - 1) / X3_C23_TARGET;
   if (spw < X3_C23_MINS) spw = X3_C23_MINS;
   const float isc = 1.f / (float)(1 << X3_W0_SHIFT);
   const dim3 grid((unsigned)((nsamp + spw - 1) / spw), P);
-  if (X3_FWD_TILE == 2 || X3_FWD_TILE == 3)
-    conv23_fwd_tile_x3<C2, C3, true><<<grid, 256, 0, st>>>(
-        (const uint16_t*)X, xlo, (uint16_t*)Y1, y1lo, (uint8_t*)bits1, br1, (const uint16_t*)Wc1, w1lo, bias1_off, chunk1,
-        (uint16_t*)Y2, y2lo, (uint8_t*)bits2, br2, (const uint16_t*)Wc2, w2lo, bias2_off, chunk2, flat, ai, ac, layer, L,
-        M, P, E, T, t0, (int)spw, isc, os1, os2);
-  else
-    conv23_fwd_tile_x3<C2, C3, false><<<grid, 256, 0, st>>>(
-        (const uint16_t*)X, xlo, (uint16_t*)Y1, y1lo, (uint8_t*)bits1, br1, (const uint16_t*)Wc1, w1lo, bias1_off, chunk1,
-        (uint16_t*)Y2, y2lo, (uint8_t*)bits2, br2, (const uint16_t*)Wc2, w2lo, bias2_off, chunk2, flat, ai, ac, layer, L,
-        M, P, E, T, t0, (int)spw, isc, os1, os2);
+  conv23_fwd_tile_x3<C2, C3><<<grid, 256, 0, st>>>(
+      (const uint16_t*)X, xlo, (uint16_t*)Y1, y1lo, (uint8_t*)bits1, br1, (const uint16_t*)Wc1, w1lo, bias1_off, chunk1,
+      (uint16_t*)Y2, y2lo, (uint8_t*)bits2, br2, (const uint16_t*)Wc2, w2lo, bias2_off, chunk2, flat, ai, ac, layer, L,
+      M, P, E, T, t0, (int)spw, isc, os1, os2);
   const int rc = (int)hipGetLastError();
   return rc ? -rc : 1;
 }
@@ -4645,7 +3911,7 @@ int x3_conv1_ring_wgrad(const void* frames, const void* fc, const float* Gr, con
   const dim3 grid((unsigned)((units + upw - 1) / upw), P);
   // env-major unit order in the atomic mode (the deterministic mode keeps the committed partition of its fixed-point
   // partial sums, so its runs repeat bit for bit)
-  const int pm = X3_SLAB_PMAP | ((X3_C1_EMAJ && !g_fx_accum) ? 2 : 0);
+  const int pm = 1 | ((X3_C1_EMAJ && !g_fx_accum) ? 2 : 0);      // position map 1, bit 1 = env-major
   if (X3_C1_WG_NCX == 2 && X3_WGRAD_PF != 1)       // 2 tiles per pass: two stages in flight fit (162 VGPRs)
     conv_wgrad_slab_x3<C1, 2, 2, true, 2><<<grid, 256, 0, st>>>(frames, 0, Gr, (const uint8_t*)bits, grad, w_off,
                                                                 b_off, chunk, ai, ac, 0, L, M, P, E, T, br, (int)upw,
@@ -4688,11 +3954,11 @@ int x3_conv_wgrad(const void* X, long xlo, int u8in, const float* Gr, const void
     if (pf == 2)
       conv_wgrad_slab_x3<Gx, OB, 2><<<grid, 256, 0, st>>>(X, xlo, Gr, (const uint8_t*)bits, grad, w_off, b_off, chunk,
                                                           ai, ac, layer, L, M, P, E, T, br, (int)upw, is, gs, nullptr,
-                                                          0, gamax, X3_SLAB_PMAP, g_fx_accum, 0);
+                                                          0, gamax, 1, g_fx_accum, 0);
     else
       conv_wgrad_slab_x3<Gx, OB, 1><<<grid, 256, 0, st>>>(X, xlo, Gr, (const uint8_t*)bits, grad, w_off, b_off, chunk,
                                                           ai, ac, layer, L, M, P, E, T, br, (int)upw, is, gs, nullptr,
-                                                          0, gamax, X3_SLAB_PMAP, g_fx_accum, 0);
+                                                          0, gamax, 1, g_fx_accum, 0);
     const int rc = (int)hipGetLastError();
     return rc ? -rc : 1;
   };
@@ -4701,7 +3967,7 @@ int x3_conv_wgrad(const void* X, long xlo, int u8in, const float* Gr, const void
     if (xlo <= 0) return -22;
     return slab(Tag<C2>{}, std::integral_constant<int, 7>{});
   }
-  if (x3_is<C3>(Hin, Win, Cin, KH, KW, S, u8in) && X3_WG3_TILE) {
+  if (x3_is<C3>(Hin, Win, Cin, KH, KW, S, u8in)) {
     if (xlo <= 0) return -22;
     const long nsamp = (long)T * E;
     long spw = (nsamp * P + X3_WG3_TARGET - 1) / X3_WG3_TARGET;   // ~X3_WG3_TARGET workgroups over the launch
@@ -4709,18 +3975,6 @@ int x3_conv_wgrad(const void* X, long xlo, int u8in, const float* Gr, const void
     conv_wgrad_tile_x3<C3><<<dim3((unsigned)((nsamp + spw - 1) / spw), P, 2), WT3<C3>::NT, 0, st>>>(
         (const uint16_t*)X, xlo, Gr, (const uint8_t*)bits, grad, w_off, b_off, chunk, ai, ac, layer, L, M, P, E, T, br,
         (int)spw, is, gs, gamax, g_fx_accum);
-    const int rc = (int)hipGetLastError();
-    return rc ? -rc : 1;
-  }
-  if (x3_is<C3>(Hin, Win, Cin, KH, KW, S, u8in)) {
-    if (xlo <= 0) return -22;
-    const long rows = (long)T * E * C3::HOWO;
-    long rpc = (rows + 15) / 16;
-    rpc = (rpc + X3_WG_RB - 1) / X3_WG_RB * X3_WG_RB;
-    if (rpc < X3_WG_RB * 4) rpc = X3_WG_RB * 4;
-    conv_wgrad_x3<C3><<<dim3((unsigned)((rows + rpc - 1) / rpc), P), 512, 0, st>>>(
-        (const bf16_t*)X, xlo, Gr, (const uint8_t*)bits, grad, w_off, b_off, chunk, ai, ac, layer, L, M, P, E, T, br,
-        (int)rpc, is, gs, gamax, g_fx_accum);
     const int rc = (int)hipGetLastError();
     return rc ? -rc : 1;
   }
@@ -4752,22 +4006,22 @@ int x3_conv_dgrad(const float* Gr, const void* bits, const float* flat, long w_o
             Gr, (const uint8_t*)bits, flat, w_off, chunk, ai, ac, layer, L, M, P, E, T, br, gs, dX, spw, gamax,      \
             gamax_out, X3_PRESPLIT);                                                                               \
     } else if (X3_DG_FOLD == 2 && X3_DG_BAL) {     /* the same workgroup count, cost-balanced, 1-D */          \
-      const size_t pad = X3_DG_CAP ? lds_cap_pad<conv_dgrad_x3<Gx, false, true, true>, 2>() : 0;                  \
+      const size_t pad = lds_cap_pad<conv_dgrad_x3<Gx, false, true, true>, 2>();                  \
       conv_dgrad_x3<Gx, false, true, true><<<dim3(grid.x * P), 256, pad, st>>>(                                    \
           Gr, (const uint8_t*)bits, flat, w_off, chunk, ai, ac, layer, L, M, P, E, T, br, gs, dX, spw, gamax,        \
           gamax_out, X3_PRESPLIT);                                                                                 \
     } else if (X3_DG_FOLD == 2) {                                                                                  \
-      const size_t pad = X3_DG_CAP ? lds_cap_pad<conv_dgrad_x3<Gx, false, true>, 2>() : 0;                        \
+      const size_t pad = lds_cap_pad<conv_dgrad_x3<Gx, false, true>, 2>();                        \
       conv_dgrad_x3<Gx, false, true><<<grid, 256, pad, st>>>(Gr, (const uint8_t*)bits, flat, w_off, chunk, ai, ac,  \
                                                              layer, L, M, P, E, T, br, gs, dX, spw, gamax,          \
                                                              gamax_out, X3_PRESPLIT);                               \
     } else if (X3_DG_W3) {                                                                                         \
-      const size_t pad = X3_DG_CAP ? lds_cap_pad<conv_dgrad_x3<Gx, true, false>, 2>() : 0;                        \
+      const size_t pad = lds_cap_pad<conv_dgrad_x3<Gx, true, false>, 2>();                        \
       conv_dgrad_x3<Gx, true><<<grid, 256, pad, st>>>(Gr, (const uint8_t*)bits, flat, w_off, chunk, ai, ac, layer, \
                                                       L, M, P, E, T, br, gs, dX, spw, gamax, gamax_out,              \
                                                       X3_PRESPLIT);                                                 \
     } else {                                                                                                       \
-      const size_t pad = X3_DG_CAP ? lds_cap_pad<conv_dgrad_x3<Gx, false, false>, 2>() : 0;                       \
+      const size_t pad = lds_cap_pad<conv_dgrad_x3<Gx, false, false>, 2>();                       \
       conv_dgrad_x3<Gx><<<grid, 256, pad, st>>>(Gr, (const uint8_t*)bits, flat, w_off, chunk, ai, ac, layer, L, M,  \
                                                 P, E, T, br, gs, dX, spw, gamax, gamax_out, X3_PRESPLIT);            \
     }                                                                                                              \
@@ -4820,8 +4074,6 @@ int x3_fc_fwd(const void* X, long xlo, int ldx, void* Y, long ylo, void* bits, c
   }
   if ((long)T * E <= 16) {
     if (of) FCX(1, 4, 0, true); else FCX(1, 4, 0, false);
-  } else if (KP == 1408 && X3_FC_D <= 2) {
-    if (of) FCX(2, 2, 44, true); else FCX(2, 2, 44, false);
   } else if (KP == 1408) {
     if (of) FCX(2, 4, 44, true); else FCX(2, 4, 44, false);
   } else if (KP == 256) {
@@ -4845,13 +4097,10 @@ int x3_fc_heads_fwd(const void* X, long xlo, int ldx, float* Y, void* bits, cons
       chunk <= 0 || L <= 0 || M <= 0 || P <= 0 || E <= 0 || t0 < 0 || br <= 0 || bias_off < 0 || xlo <= 0 ||
       wlo <= 0 || A <= 0) return -22;
   if (M > X3_MAXM || Cout != 256 || K != 256 || KP != 256 || ldx % 8 != 0 || ldx < KP || E > 32 || A > 8) return 0;
-#define FHX(D_)                                                                                                    \
-  fc_heads_fwd_x3<8, D_><<<dim3((unsigned)((E + 15) / 16), (unsigned)P), 256, 0, st>>>(                             \
-      (const uint16_t*)X, xlo, ldx, Y, (uint16_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac, layer, \
-      L, M, P, E, t0, br, 1.f / (float)(1 << X3_W0_SHIFT), os, pw, pb, vw, vb, A, logits, value, actions, seed, ctr, t,  \
-      Tsteps, greedy, rb)
-  if (X3_FH_D >= 3) FHX(3); else FHX(2);
-#undef FHX
+  fc_heads_fwd_x3<8, 3><<<dim3((unsigned)((E + 15) / 16), (unsigned)P), 256, 0, st>>>(
+      (const uint16_t*)X, xlo, ldx, Y, (uint16_t*)bits, (const uint16_t*)Wc, wlo, flat, bias_off, chunk, ai, ac, layer,
+      L, M, P, E, t0, br, 1.f / (float)(1 << X3_W0_SHIFT), os, pw, pb, vw, vb, A, logits, value, actions, seed, ctr, t,
+      Tsteps, greedy, rb);
   const int rc = (int)hipGetLastError();
   return rc ? -rc : 1;
 }
@@ -4878,7 +4127,9 @@ int x3_fc_fwd_mm(const void* X, long xlo, int ldx, void* Y, long ylo, void* bits
     // 48.1 (2) / 46.1 (3) / 51.5 (4) us: at two workgroups per CU, 3 parts keep the ~280 units of 64 paths in one
     // round of 512 slots where 4 parts spill into a second)
     else if (X3_FC_MMV == 3) ks = (long)P * R <= 768 ? 4 : 3;
-    while (ks > 2 && (KP / 32) / ks < 2) ks >>= 1;           // every part keeps >= 2 k-steps
+    // every part keeps >= 2 k-steps: down the instantiated part counts 8 -> 4 -> 2 and 3 -> 2 (a halving took 3 to 1,
+    // whose launch below is the 2-part kernel on a 1-part grid)
+    while (ks > 2 && (KP / 32) / ks < 2) ks = ks == 8 ? 4 : 2;
     const int umax = (ks * M * 2 * ((P * R + 127) / 128) + 7) / 8 * 8;
     const unsigned g2 = (unsigned)(((long)P * R * 32 + 255) / 256);
 #define MM2KS(KS_)                                                                                                \
@@ -4981,7 +4232,7 @@ int x3_fc_wgrad_gm(const void* X, long xlo, int ldx, const void* Gm, long gmlo, 
   if (ldx <= 0 || chunk <= 0 || M <= 0 || Pmax <= 0 || K <= 0 || Cout <= 0 || P <= 0 || E <= 0 || T <= 0 || br <= 0 ||
       nsplit <= 0 || w_off < 0 || b_off < 0 || layer < 0 || xlo <= 0 || gmlo <= 0 || !gamax) return -22;
   if (Cout != 256 || ldx % 8 != 0 || K % 8 != 0) return 0;
-  if (X3_FCW_KT == 256 && K > 256) {
+  if (K > 256) {
     // 256-wide k tiles: the masked gradient Gm (1 KB per row) is re-read once per k tile -- 6 instead of 11 times at
     // K = 1408
     const int kt = (K + 255) / 256;

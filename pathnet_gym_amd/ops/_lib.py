@@ -166,23 +166,13 @@ _SIGS = {
     "x3_status_fold": [P, P, P],
     "x3_set_fx": [P],
     "x3_fx_flush": [P, P, c_long, c_long, P],
-    "fast_conv_set_x3_fwd_nt": [c_int],
-    "fast_conv_set_x3_fwd_lb": [c_int],
-    "fast_conv_set_x3_fwd_db": [c_int],
-    "fast_conv_set_x3_fwd_sw": [c_int],
-    "fast_conv_set_x3_wg3_tile": [c_int],
     "fast_conv_set_x3_fc_mmv": [c_int],
     "fast_conv_set_x3_fc_dg_gemm": [c_int],
-    "fast_conv_set_x3_fcw_kt": [c_int],
     "fast_conv_set_x3_dg_w3": [c_int],
     "fast_conv_set_x3_c1_f16b": [c_int],
     "fast_conv_set_x3_dg_fold": [c_int],
-    "fast_conv_set_x3_fwd_tile": [c_int],
-    "fast_conv_set_x3_c1_band": [c_int],
-    "fast_conv_set_x3_c1_pipe": [c_int],
     "heads_set_s16": [c_int],
     "heads_set_bwd_rows": [c_int],
-    "fast_conv_set_x3_fc_d": [c_int],
     "fast_conv_set_x3_fc_ks": [c_int],
     "fast_conv_set_x3_wgrad_pf": [c_int],
     "fast_conv_set_x3_c1_wg_ncx": [c_int],
@@ -197,10 +187,8 @@ _SIGS = {
     "fast_conv_set_x3_c23_mins": [c_int],
     "fast_conv_set_x3_fcw_target": [c_int],
     "fast_conv_set_x3_dg3_target": [c_int],
-    "fast_conv_set_x3_slab_pmap": [c_int],
     "fast_conv_set_x3_c1_sb1": [c_int],
     "fast_conv_set_x3_presplit": [c_int],
-    "fast_conv_set_x3_fh_d": [c_int],
     "fast_conv_set_x3_dg_target": [c_int],
     "fast_conv_set_x3_fc_ks_parts": [c_int],
     "conv_fwd_smem": [c_int, c_int],

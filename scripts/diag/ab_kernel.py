@@ -2,7 +2,7 @@
 same data: a bench window per setting drifts by +-10 % between runs on one box (clock / thermal state), which
 swamps a 5 % kernel change.  Example:
 
-    python scripts/diag/ab_kernel.py --kernel ring_wgrad --opt x3_slab_pmap=0 --opt x3_slab_pmap=1
+    python scripts/diag/ab_kernel.py --kernel ring_wgrad --opt x3_c1_emaj=0 --opt x3_c1_emaj=1
 """
 import argparse
 import json
