@@ -135,13 +135,17 @@ DEVI void heads_fma(float (&acc)[AW], float x, const float* w) {
   if constexpr (AW % 2) acc[AW - 1] = __builtin_fmaf(x, w[AW - 1], acc[AW - 1]);
 }
 
-// action-sampling RNG (heads.hip Gumbel-max, trunk_x3.hip fused heads): a uniform in (0, 1) keyed by
-// (seed, update counter x step, sample, action)
+// action-sampling RNG (heads.hip Gumbel-max, trunk_x3.hip fused heads, envs.hip fused env heads): a uniform
+// strictly inside (0, 1) keyed by (seed, update counter x step, sample, action).  k = h >> 8 is 24 bits.  Below 2^23
+// the +0.5 is exact and u = (k + 0.5) 2^-24 is the centre of its cell; from 2^23 on fp32 has no half steps and k + 0.5
+// rounds to even (k or k + 1), which moves a draw by half a cell at most (harmless) -- except at k = 2^24 - 1,
+// where it reaches 2^24 and u would be exactly 1: -log(-log(1)) = +inf, and that action would win whatever its
+// logit.  The clamp to the largest fp32 below 1 changes that one draw in 2^24 and no other.
 DEVI float sample_u01(uint32_t seed, uint32_t stepkey, uint32_t b, uint32_t j) {
   uint32_t h = wang_hash(stepkey * 64u + j);
   h = wang_hash(h ^ b);
   h = wang_hash(h ^ seed);
-  return ((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  return fminf(((float)(h >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 DEVI uint32_t env_rand_u32(uint32_t seed, uint32_t env_id, uint32_t counter, uint32_t stream) {

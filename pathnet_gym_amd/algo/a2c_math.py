@@ -73,16 +73,26 @@ def sample_actions(logits: torch.Tensor, generator=None) -> torch.Tensor:
     return torch.multinomial(probs, 1, generator=generator).squeeze(1)
 
 
+def hash_to_u01(h: torch.Tensor) -> torch.Tensor:
+    """common.h sample_u01's last line: a 32-bit hash (int64 tensor) -> fp32 uniform strictly inside (0, 1)."""
+    u = ((h >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
+    return u.clamp(max=1.0 - 2.0 ** -24)                                     # 0x1.fffffep-1f
+
+
 def sampling_u01(seed: int, stepkey: int, rows: torch.Tensor, A: int) -> torch.Tensor:
     """The uniforms of the HIP heads kernel's Gumbel-max (csrc/heads.hip u01), bit for bit: hash(stepkey * 64 +
-    action) -> ^ global row -> ^ seed, 24 bits, centred.  rows: int64 [N] global sample indices.  [N, A] fp32."""
+    action) -> ^ global row -> ^ seed, k = the top 24 bits, u = fp32(k + 0.5) * 2^-24 clamped to the largest fp32
+    below 1.  Below k = 2^23 that is the centre of the k-th cell; from 2^23 on fp32 has no half steps and k + 0.5
+    rounds to even (harmless), which at k = 2^24 - 1 would give exactly 1 and a Gumbel noise of +inf: the clamp
+    (common.h sample_u01) keeps every draw strictly inside (0, 1).  rows: int64 [N] global sample indices.
+    [N, A] fp32."""
     from ..envs.base import wang_hash
     m = 0xFFFFFFFF
     j = torch.arange(A, dtype=torch.int64, device=rows.device)
     h = wang_hash(torch.full_like(j, (stepkey * 64) & m) + j)[None, :]        # [1, A]
     h = wang_hash(h ^ (rows[:, None] & m))
     h = wang_hash(h ^ (seed & m))
-    return ((h >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
+    return hash_to_u01(h)
 
 
 def sample_actions_keyed(logits: torch.Tensor, seed: int, stepkey: int, row_base: int = 0,

@@ -501,7 +501,7 @@ def test_heads_sampling_row_base_and_torch_keyed_sampler(hip_lib):
     P, E = 4, 16
     m = make_model(cfg, P, random_masks(P, cfg.L, cfg.M, cfg.N, with_edge=False))
     B = P * E
-    feat = torch.randn(B, 128, device=DEV).to(torch.bfloat16)
+    feat = torch.randn(B, 128, generator=torch.Generator().manual_seed(5)).to(DEV).to(torch.bfloat16)
     ctr = torch.full((1,), 3, dtype=torch.int64, device=DEV)
     outs = []
     for k in (0, 16):
@@ -512,9 +512,12 @@ def test_heads_sampling_row_base_and_torch_keyed_sampler(hip_lib):
         outs.append((logits, actions))
     torch.cuda.synchronize()
     assert torch.equal(outs[1][1], outs[0][1][16:])
+    # __logf vs torch.log: only near-ties may differ.  The rule of test_heads_kernels.py: the kernel's action is the
+    # float64 Gumbel argmax on every row whose top-two gap is at least 8 e32, and the torch sampler obeys it too
+    import test_heads_kernels as thk
     ta = sample_actions_keyed(outs[0][0], 99, 3 * 5 + 2, 0)
-    agree = (ta.cpu() == outs[0][1].long().cpu()).float().mean().item()
-    assert agree > 0.98, agree            # __logf vs torch.log: only near-ties may differ
+    for tag, a in (("hip", outs[0][1]), ("torch", ta)):
+        thk.check_sampler_agreement(outs[0][0], a, 99, 3 * 5 + 2, 0, f"row_base test, {tag}", record=False)
 
 
 @pytest.mark.parametrize("rows", [32, 128])
@@ -1584,11 +1587,13 @@ def test_supervised_hip_backend_trains(hip_lib):
     assert accs[-1] > 0.5
 
 
-@pytest.mark.parametrize("window", [0, 3])
-def test_fitness_update_kernel_matches_reference(hip_lib, window):
-    """Per-path fitness from the rollout's (done, episode return) pairs (a3c_training_thread.py:145-147)."""
+@pytest.mark.parametrize("window,T", [pytest.param(0, 7, id="0"), pytest.param(3, 7, id="3"),
+                                      pytest.param(3, 70, id="3-T70")])
+def test_fitness_update_kernel_matches_reference(hip_lib, window, T):
+    """Per-path fitness from the rollout's (done, episode return) pairs (a3c_training_thread.py:145-147).  T = 70 is
+    more than the kernel's 64 threads: the t += blockDim.x loop and 2 T floats of dynamic LDS."""
     from pathnet_gym_amd.ops import _lib
-    T, P, E = 7, 5, 48
+    P, E = 5, 48
     rng = np.random.RandomState(4)
     dones = (rng.rand(T, P, E) < 0.05).astype(np.uint8)
     dones[:, 3, :] = 0                                   # a path with no finished episode keeps its fitness
