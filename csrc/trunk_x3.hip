@@ -2617,15 +2617,19 @@ __global__ __launch_bounds__(512) void fc_fwd_mm_x3(const uint16_t* __restrict__
 // ===========================================================================
 DEVI int mm2_sw(int row, int ch) { return (row << 2) + (ch ^ ((-(row >> 2)) & 3)); }   // 16-byte chunk index
 
-template <int NKS, int PF, int KS>
-__global__ __launch_bounds__(512, 2) void fc_fwd_mm2_x3(const uint16_t* __restrict__ X, long xlo, int ldx,
-                                                       float* __restrict__ Ys, uint16_t* __restrict__ bits,
-                                                       const uint16_t* __restrict__ Wc, long wlo,
-                                                       const float* __restrict__ flat, long bias_off, int chunk,
-                                                       const int* __restrict__ inv_path,
-                                                       const int* __restrict__ inv_slot,
-                                                       const int* __restrict__ inv_cnt, int layer, int M, int KP, int P,
-                                                       int E, int T, int t0, long bits_rows, float in_scale) {
+// WPE: the launch bound's second argument is waves per SIMD, not workgroups per CU.  Two 8-wave workgroups on a CU
+// are 4 waves per SIMD, so 128 VGPRs at the most; with WPE = 2 the runtime-count build (NKS = 0, fc1) took 137 and
+// ran one workgroup per CU, its ~420 workgroups at 64 paths in two rounds.  WPE = 2 stays as the comparison arm and
+// for KS = 1 (which spills under the 128 cap).
+template <int NKS, int PF, int KS, int WPE>
+__global__ __launch_bounds__(512, WPE) void fc_fwd_mm2_x3(const uint16_t* __restrict__ X, long xlo, int ldx,
+                                                         float* __restrict__ Ys, uint16_t* __restrict__ bits,
+                                                         const uint16_t* __restrict__ Wc, long wlo,
+                                                         const float* __restrict__ flat, long bias_off, int chunk,
+                                                         const int* __restrict__ inv_path,
+                                                         const int* __restrict__ inv_slot,
+                                                         const int* __restrict__ inv_cnt, int layer, int M, int KP, int P,
+                                                         int E, int T, int t0, long bits_rows, float in_scale) {
   constexpr int COUT = 256, BR = 128, BC = 128, NCS = COUT / BC, NWORDS = COUT / 16;
   __shared__ __attribute__((aligned(16))) uint16_t As[2][2][BR * 32];
   __shared__ __attribute__((aligned(16))) uint16_t Bs[2][2][BC * 32];
@@ -3666,6 +3670,10 @@ static int X3_FC_KS = 1;
 // fragments), 2 = fc_fwd_mm2_x3 (LDS-staged 128 x 128 tiles), 3 = the same with k split in two workgroups
 // (pre-activation planes; bias, ReLU, bits and the slot sum in fc_slot_sum2_x3)
 static int X3_FC_MMV = 3;
+// fc_fwd_mm2_x3 with a runtime k-step count (fc1), k split: waves per SIMD its build is bounded for.  4 = two
+// workgroups per CU (128 VGPRs), 2 = the 137-VGPR build that runs one per CU (the comparison arm), 0 = by rows
+// (x3_fc_fwd_mm)
+static int X3_FC_FWD_WPE = 0;
 static int X3_C1_F16B = 1;     // band forward: 1 = the band converted to fp16 once at staging (conv1_fwd_band_x2 F16B;
                                // interleaved A/B: 64 paths 97.1 -> 95.8 us, 8 paths 20.9 -> 20.4)
 static int X3_C1_SB1 = 0;      // band forward (ring): 1 = one band buffer, three workgroups per CU (conv1_fwd_band_x2 SB1)
@@ -3747,6 +3755,7 @@ int x3_fx_flush(void* fx, float* grad, long n0, long n1, hipStream_t st) {
 
 void fast_conv_set_x3_c1_wg_ncx(int v) { X3_C1_WG_NCX = v == 2 ? 2 : 3; }
 void fast_conv_set_x3_fc_mmv(int v) { X3_FC_MMV = v; }
+void fast_conv_set_x3_fc_fwd_wpe(int v) { X3_FC_FWD_WPE = v == 2 || v == 4 ? v : 0; }
 void fast_conv_set_x3_fc_dg_gemm(int v) { X3_FC_DG_GEMM = v; }
 void fast_conv_set_x3_dg_w3(int v) { X3_DG_W3 = v; }
 void fast_conv_set_x3_dg_fold(int v) { X3_DG_FOLD = v; }
@@ -4125,23 +4134,35 @@ int x3_fc_fwd_mm(const void* X, long xlo, int ldx, void* Y, long ylo, void* bits
     // 4 parts up to 768 rows, else 3 (layer A/B, profiles/r5/ab_ks*.json: 8 paths 22.0 (8 parts) -> 21.6, 16 paths
     // 27.9 (2) -> 23.9, 24 paths 28.7 (2) / 26.1 (3) / 24.8 (4); 32 paths 29.3 (2) / 28.7 (3) / 33.9 (4); 64 paths
     // 48.1 (2) / 46.1 (3) / 51.5 (4) us: at two workgroups per CU, 3 parts keep the ~280 units of 64 paths in one
-    // round of 512 slots where 4 parts spill into a second)
+    // round of 512 slots where 4 parts spill into a second).  Those figures were taken with the 137-VGPR build, which
+    // ran ONE workgroup per CU (wpe below); the part counts stay as they are, since they fix the summation order
     else if (X3_FC_MMV == 3) ks = (long)P * R <= 768 ? 4 : 3;
     // every part keeps >= 2 k-steps: down the instantiated part counts 8 -> 4 -> 2 and 3 -> 2 (a halving took 3 to 1,
     // whose launch below is the 2-part kernel on a 1-part grid)
     while (ks > 2 && (KP / 32) / ks < 2) ks = ks == 8 ? 4 : 2;
     const int umax = (ks * M * 2 * ((P * R + 127) / 128) + 7) / 8 * 8;
     const unsigned g2 = (unsigned)(((long)P * R * 32 + 255) / 256);
+    // the two-per-CU build above 1024 rows, where the grid outgrows one workgroup per CU (layer A/B,
+    // profiles/r7/ab_fc1_fwd.jsonl: 48 paths 42.6 -> 39.8 us, 64 paths 45.5 -> 41.9; 32 paths 28.9 both; 8 / 16 / 24
+    // paths 21.5 / 23.5 / 24.5 -> 21.9 / 23.8 / 24.8: with a CU to itself the 137-VGPR build is the faster one)
+    const int wpe = X3_FC_FWD_WPE ? X3_FC_FWD_WPE : ((long)P * R > 1024 ? 4 : 2);
 #define MM2KS(KS_)                                                                                                \
     {                                                                                                             \
       if (KP == 256)                                                                                              \
-        fc_fwd_mm2_x3<8, 3, KS_><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,          \
-                                                       (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path,  \
-                                                       inv_slot, inv_cnt, layer, M, KP, P, E, T, t0, br, isc);     \
+        fc_fwd_mm2_x3<8, 3, KS_, 2><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,       \
+                                                          (const uint16_t*)Wc, wlo, flat, bias_off, chunk,         \
+                                                          inv_path, inv_slot, inv_cnt, layer, M, KP, P, E, T, t0,  \
+                                                          br, isc);                                                \
+      else if (wpe == 2)                                                                                          \
+        fc_fwd_mm2_x3<0, 3, KS_, 2><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,       \
+                                                          (const uint16_t*)Wc, wlo, flat, bias_off, chunk,         \
+                                                          inv_path, inv_slot, inv_cnt, layer, M, KP, P, E, T, t0,  \
+                                                          br, isc);                                                \
       else                                                                                                        \
-        fc_fwd_mm2_x3<0, 3, KS_><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,          \
-                                                       (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path,  \
-                                                       inv_slot, inv_cnt, layer, M, KP, P, E, T, t0, br, isc);     \
+        fc_fwd_mm2_x3<0, 3, KS_, 4><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,       \
+                                                          (const uint16_t*)Wc, wlo, flat, bias_off, chunk,         \
+                                                          inv_path, inv_slot, inv_cnt, layer, M, KP, P, E, T, t0,  \
+                                                          br, isc);                                                \
       int rc_ = (int)hipGetLastError();                                                                           \
       if (rc_) return -rc_;                                                                                       \
       if (ylo == 0)                                                                                               \
@@ -4158,13 +4179,13 @@ int x3_fc_fwd_mm(const void* X, long xlo, int ldx, void* Y, long ylo, void* bits
   } else if (X3_FC_MMV >= 2) {
     const int umax = (M * 2 * ((P * R + 127) / 128) + 7) / 8 * 8;    // every module on every path: an upper bound
     if (KP == 256)
-      fc_fwd_mm2_x3<8, 3, 1><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,
-                                                   (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path, inv_slot,
-                                                   inv_cnt, layer, M, KP, P, E, T, t0, br, isc);
+      fc_fwd_mm2_x3<8, 3, 1, 2><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,
+                                                      (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path,
+                                                      inv_slot, inv_cnt, layer, M, KP, P, E, T, t0, br, isc);
     else
-      fc_fwd_mm2_x3<0, 3, 1><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,
-                                                   (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path, inv_slot,
-                                                   inv_cnt, layer, M, KP, P, E, T, t0, br, isc);
+      fc_fwd_mm2_x3<0, 3, 1, 2><<<umax, 512, 0, st>>>((const uint16_t*)X, xlo, ldx, Ys, (uint16_t*)bits,
+                                                      (const uint16_t*)Wc, wlo, flat, bias_off, chunk, inv_path,
+                                                      inv_slot, inv_cnt, layer, M, KP, P, E, T, t0, br, isc);
   } else {
     const int umax = M * ((P * tpp + 3) / 4) * 2;    // x 2 column slices (fc_fwd_mm_x3 NH)
     const int nwg = (umax + 7) / 8 * 8;

@@ -167,6 +167,7 @@ _SIGS = {
     "x3_set_fx": [P],
     "x3_fx_flush": [P, P, c_long, c_long, P],
     "fast_conv_set_x3_fc_mmv": [c_int],
+    "fast_conv_set_x3_fc_fwd_wpe": [c_int],
     "fast_conv_set_x3_fc_dg_gemm": [c_int],
     "fast_conv_set_x3_dg_w3": [c_int],
     "fast_conv_set_x3_c1_f16b": [c_int],
