@@ -276,15 +276,21 @@ class HipPathNet:
         lay_h = lay.heads
         self.heads_off = lay_h
         # fused LSTM cell: csrc/lstm.hip (bf16 copies of the fp32 master kernel) or, in fp32x, csrc/lstm_x3.hip (fp16
-        # hi+lo pairs, fp32 state: the reference's default network at its precision).  fp32 (deterministic) keeps
-        # the hybrid autograd LSTM.
+        # hi+lo pairs, fp32 state: the reference's default network at its precision) or, in fp32, csrc/lstm_f32.hip
+        # (fp32 operands read from the flat master, fixed-order reductions: no operand copies, a partial-slab
+        # scratch for the weight gradient).  PATHNET_F32_LSTM=0 keeps the hybrid autograd LSTM for fp32 (A/B runs).
+        # The bf16 engine with deterministic=True keeps the hybrid path too: its features are bf16 and an ordered
+        # bf16 cell is out of scope.
         self.lstm = None
-        if cfg.use_lstm and not self.deterministic:
+        f32_lstm = self.f32 and os.environ.get("PATHNET_F32_LSTM", "1") != "0"
+        if cfg.use_lstm and (f32_lstm or not self.deterministic):
             ls = lay.lstm
             F, H = ls["din"], ls["H"]
-            if F % 64 == 0 and H % 64 == 0:
+            if F % 64 == 0 and H % 64 == 0 and f32_lstm:
+                self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=False, f32=True, part=None)
+            elif F % 64 == 0 and H % 64 == 0:
                 pl = (2,) if self.x3 else ()
-                self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=self.x3,
+                self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=self.x3, f32=False,
                                  KpT=torch.zeros(pl + (4 * H, F + H), dtype=torch.float16 if self.x3 else torch.bfloat16,
                                                  device=dev),
                                  Kb=torch.zeros(pl + (F + H, 4 * H), dtype=torch.float16 if self.x3 else torch.bfloat16,
@@ -433,22 +439,35 @@ class HipPathNet:
             for buf, f16 in ((self.Wc_ring, 0), (self.Wh_ring, 1)):
                 _lib.call("launch_refresh_weights_cmajor", flat.data_ptr(), g.w_off, g.chunk, g.KH, g.KW, g.Cin,
                           g.Cout, self.M, buf.data_ptr(), f16, _lib.stream())
-        if self.lstm is not None:
+        if self.lstm is not None and not self.lstm["f32"]:     # csrc/lstm_f32.hip reads the flat master itself
             ls = self.lstm
             _lib.call("launch_lstm_refresh", flat.data_ptr(), ls["k_off"], ls["F"], ls["H"], ls["KpT"].data_ptr(),
                       ls["Kb"].data_ptr(), _lib.stream())
 
-    # -- fused LSTM cell (csrc/lstm.hip) ------------------------------------------
+    # -- fused LSTM cell (csrc/lstm.hip, csrc/lstm_x3.hip, csrc/lstm_f32.hip) ------
     @property
     def lstm_dtype(self):
-        """dtype of the LSTM hidden state / saved [x | h] rows: fp32 in fp32x, bf16 otherwise."""
-        return torch.float32 if self.x3 else torch.bfloat16
+        """dtype of the LSTM hidden state / saved [x | h] rows: fp32 in fp32x and fp32, bf16 otherwise."""
+        return torch.float32 if (self.x3 or self.f32) else torch.bfloat16
 
-    def lstm_prepare(self, T: int):
-        """fp32x: size the G16 amax slots for a T-step rollout (before any graph capture)."""
+    def lstm_prepare(self, T: int, B: int = 0):
+        """Buffers sized by the rollout, allocated before any graph capture.  fp32x: the G16 amax slots of a T-step
+        rollout; fp32: the weight gradient's partial slabs for the T * B rows of a rollout of B agents
+        (csrc/lstm_f32.hip; without B they are allocated by the first lstm_wgrad, which must then run eagerly)."""
         ls = self.lstm
+        if ls is not None and ls["f32"] and B > 0:
+            self._lstm_part(T * B)
         if ls is not None and ls["x3"] and ls["amax"].numel() < T + 1:
             ls["amax"] = torch.zeros(T + 1, dtype=torch.float32, device=ls["amax"].device)
+
+    def _lstm_part(self, R: int) -> torch.Tensor:
+        ls = self.lstm
+        n = _lib.lib().lstm_wgrad_f32_part_numel(ls["F"], ls["H"], R)
+        if ls["part"] is None or ls["part"].numel() < n:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LSTM weight-gradient partials first needed inside a graph capture")
+            ls["part"] = torch.empty(n, dtype=torch.float32, device=self.model.device)
+        return ls["part"]
 
     def lstm_amax_reset(self):
         """fp32x: zero the G16 amaxes at the start of a rollout (the forward's xh rows, then the backward's dz)."""
@@ -466,6 +485,12 @@ class HipPathNet:
             _lib.check(t, dt, numel=B * ls["H"], name=nm)
         if xh is not None:
             _lib.check(xh, dt, numel=B * (ls["F"] + ls["H"]), name="xh")
+        if ls["f32"]:
+            flat = self.model.store.flat
+            _lib.call("launch_lstm_fwd_f32", x.data_ptr(), x.shape[1], hprev.data_ptr(), cprev.data_ptr(),
+                      _lib.ptr(prev_done), flat.data_ptr(), ls["k_off"], ls["b_off"], hout.data_ptr(),
+                      cout.data_ptr(), _lib.ptr(gates), _lib.ptr(xh), ls["F"], ls["H"], B, _lib.stream())
+            return
         if ls["x3"]:
             _lib.call("launch_lstm_fwd_x3", x.data_ptr(), x.shape[1], hprev.data_ptr(), cprev.data_ptr(),
                       _lib.ptr(prev_done), ls["KpT"].data_ptr(), self.model.store.flat.data_ptr(), ls["b_off"],
@@ -496,12 +521,23 @@ class HipPathNet:
         _lib.call("launch_lstm_bwd_point", dh_heads.data_ptr(), _lib.ptr(dh_rec), _lib.ptr(dc_rec),
                   _lib.ptr(done_t), gates.data_ptr(), c_t.data_ptr(), c_prev.data_ptr(), _lib.ptr(prev_done),
                   dz.data_ptr(), dc_out.data_ptr(), ls["H"], B, st)
+        if ls["f32"]:
+            _lib.call("launch_lstm_bwd_gemm_f32", dz.data_ptr(), self.model.store.flat.data_ptr(), ls["k_off"],
+                      dx.data_ptr(), dx.shape[-1], dh_prev.data_ptr(), ls["F"], ls["H"], B, st)
+            return
         _lib.call("launch_lstm_bwd_gemm", dz.data_ptr(), ls["Kb"].data_ptr(), dx.data_ptr(), dx.shape[-1],
                   dh_prev.data_ptr(), ls["F"], ls["H"], B, st)
 
     def lstm_wgrad(self, xh, dz, grad_flat, rows_per_chunk: int = 2048):
+        """fp32: fixed row chunks (csrc/lstm_f32.hip LF32_CHUNK) and ordered sums; rows_per_chunk is not used."""
         ls = self.lstm
         R = xh.numel() // (ls["F"] + ls["H"])
+        if ls["f32"]:
+            _lib.check(xh, torch.float32, name="xh")
+            _lib.check(dz, torch.float32, numel=R * 4 * ls["H"], name="dz")
+            _lib.call("launch_lstm_wgrad_f32", xh.data_ptr(), dz.data_ptr(), grad_flat.data_ptr(),
+                      self._lstm_part(R).data_ptr(), ls["k_off"], ls["b_off"], ls["F"], ls["H"], R, _lib.stream())
+            return
         if ls["x3"]:
             am = ls["amax"]
             _lib.call("launch_lstm_wgrad_x3", xh.data_ptr(), dz.data_ptr(), grad_flat.data_ptr(), ls["k_off"],
@@ -512,7 +548,8 @@ class HipPathNet:
                   ls["F"], ls["H"], R, rows_per_chunk, _lib.stream())
 
     def lstm_carry(self, hT, cT, done_last, h0, c0):
-        _lib.call("launch_lstm_carry_f32" if self.lstm["x3"] else "launch_lstm_carry", hT.data_ptr(), cT.data_ptr(),
+        f32_state = self.lstm["x3"] or self.lstm["f32"]
+        _lib.call("launch_lstm_carry_f32" if f32_state else "launch_lstm_carry", hT.data_ptr(), cT.data_ptr(),
                   done_last.data_ptr(), h0.data_ptr(), c0.data_ptr(), self.lstm["H"], h0.shape[0], _lib.stream())
 
     # ------------------------------------------------------------------

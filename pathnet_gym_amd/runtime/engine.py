@@ -156,15 +156,16 @@ class HipEngine:
         # (everything but the first layer's backward) and a tail (that backward), replayed around the bucket-1
         # all-reduce (parallel/comm.py exchange_async_split)
         self.split = False
-        # LSTM nets: fused HIP LSTM cell (csrc/lstm.hip) when the widths are multiples of 64; otherwise
-        # the hybrid path (HIP trunk + autograd LSTM/heads/loss, dL/dfeat fed back to the HIP trunk backward)
+        # LSTM nets: fused HIP LSTM cell (csrc/lstm.hip; fp32x: csrc/lstm_x3.hip; fp32: csrc/lstm_f32.hip) when the
+        # widths are multiples of 64; otherwise, and in the bf16 engine's deterministic mode, the hybrid path (HIP
+        # trunk + autograd LSTM/heads/loss, dL/dfeat fed back to the HIP trunk backward: eager, never captured)
         self.lstm_hip = hp.lstm is not None
         self.hybrid = bool(model.cfg.use_lstm) and not self.lstm_hip
         self.lstm_state = model.init_state(B) if self.hybrid else None
         if self.lstm_hip:
             F, H = hp.lstm["F"], hp.lstm["H"]
-            ldt = hp.lstm_dtype                  # bf16 (bf16 engine) or fp32 (fp32x: csrc/lstm_x3.hip)
-            hp.lstm_prepare(T)
+            ldt = hp.lstm_dtype                  # bf16 (bf16 engine) or fp32 (fp32x and fp32 engines)
+            hp.lstm_prepare(T, B)
             self.hst = torch.zeros(T + 2, B, H, dtype=ldt, device=dev)   # slot t = state entering step t
             self.cst = torch.zeros(T + 2, B, H, device=dev)
             self.gates = torch.zeros(T, B, 4 * H, device=dev)
