@@ -1,5 +1,5 @@
 // On-device game logic for the synthetic Atari-style suite (envs/atari_games.py):
-// Breakout, SpaceInvaders, Alien / MsPacman, Centipede.
+// Breakout, SpaceInvaders, Alien / MsPacman, Centipede, and for the synthetic Doom scenarios (envs/doom_games.py).
 //
 // ONE thread per env runs the whole agent step: `frameskip` physics sub-frames,
 // reward / done / episode return, the auto-reset of finished envs, and the scene
@@ -639,6 +639,323 @@ struct DoomTakeCover : DoomView {
   }
 };
 
+// --------------------------------------------------------------------------- free-view Doom scenarios
+// A player with a position (px, pz) in 1/U world units and a heading th (256 units a turn, 0 looks along +z,
+// positive turns right) in a room: DoomDefendLine, DoomHealthGathering, DoomCorridor (envs/doom_games.py,
+// DoomNavVec).  Integer only: isin / icos come from the quarter-wave table QSIN[i] = round(256 sin(2 pi i / 256)).
+//
+// Painter's order without sorting: every rectangle slot has a fixed colour, objects that can overlap each other share
+// one colour, and the kinds are layered by an argument that holds in every frame.  Posts stand on the walls of a
+// convex room (the far line, the square room's walls, the corridor's side walls), so whatever inside the room
+// overlaps a post on screen is nearer than it: backdrop, posts, vest, enemies or kits, fireballs, HUD.  (Fireballs
+// are painted over every monster, as in DoomTakeCover: a glowing ball is seen through a nearer monster.)
+__constant__ int QSIN[65] = {0, 6, 13, 19, 25, 31, 38, 44, 50, 56, 62, 68, 74, 80, 86, 92, 98, 104, 109, 115, 121, 126,
+                             132, 137, 142, 147, 152, 157, 162, 167, 172, 177, 181, 185, 190, 194, 198, 202, 206, 209,
+                             213, 216, 220, 223, 226, 229, 231, 234, 237, 239, 241, 243, 245, 247, 248, 250, 251, 252,
+                             253, 254, 255, 255, 256, 256, 256};
+
+struct DoomNav : DoomView {
+  static constexpr int U = 16, ZVIEW = 160, COL = 80, DXMAX = 512;
+  static constexpr int BIG = 1 << 20;
+  struct V { int dx, dz; };
+  static DEVI int isin(int h) {
+    h = fmodi(h, 256);
+    const int k = h & 127;
+    const int q = QSIN[k <= 64 ? k : 128 - k];
+    return h >= 128 ? -q : q;
+  }
+  static DEVI int icos(int h) { return isin(h + 64); }
+  // view offset in whole world units of (rx, rz), given in 1/div units, for sn = isin(th), cs = icos(th).
+  // int32 bound: |rx|, |rz| <= 2^14 (DoomCorridor: 1000 * 16 sub-units) and |sn|, |cs| <= 2^8, so each product is at
+  // most 2^22 and their sum at most 2^23.
+  static DEVI V view(int rx, int rz, int sn, int cs, int div) {
+    return {fdiv(rx * cs - rz * sn, 256 * div), fdiv(rx * sn + rz * cs, 256 * div)};
+  }
+  static DEVI bool drawn(V v) { return v.dz >= 0 && v.dz <= ZVIEW; }
+  // the hit-scan rule: the object's drawn rectangle covers the sights' column
+  static DEVI bool covers(V v, int w) {
+    const int den = clampi(v.dz, 0, ZVIEW) + Z0;
+    const int pw = fdiv(w * K, den);
+    const int x0 = 80 + fdiv(clampi(v.dx, -DXMAX, DXMAX) * K, den) - fdiv(pw, 2);
+    return drawn(v) && x0 <= COL && COL < x0 + pw;
+  }
+  static DEVI void nav_object(int16_t* r, int i, V v, int w, int h, bool visible, int lift = 0) {
+    const int z = clampi(v.dz, 0, ZVIEW);
+    object(r, i, 80 + fdiv(clampi(v.dx, -DXMAX, DXMAX) * K, z + Z0), z, w, h, visible && drawn(v),
+           fdiv(lift * K, z + Z0));
+  }
+};
+
+struct DoomDefendLine : DoomNav {
+  static constexpr int DEATH_PENALTY = 1, TIMEOUT = 2100;
+  static constexpr int NM = 6, NF = 3, NP = 5, TURN = 2, TH_MAX = 40, DMAX = 96, STAGGER = 32, STANDOFF = 48;
+  static constexpr int MON_W = 24, MON_H = 40, SH_W = 20, SH_H = 48, POST_W = 12, POST_GAP = 48;
+  static constexpr int COOLDOWN = 8, RESPAWN = 16, HP_MAX = 3, BITE = 8, DAMAGE = 10, HEALTH = 100;
+  static constexpr int FIRE = 24, FPHASE = 8, FSPEED = 4, FDAMAGE = 6, FB_W = 12, FB_H = 12, FB_LIFT = 25;
+  enum { TH, COOL, HEALTHF, TIC, MD, MHP = MD + NM, MT = MHP + NM, MK = MT + NM, FD = MK + NM, ALIVE = FD + NF, FACT,
+         COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + NP + NM + NF + 3;
+  static DEVI int lane_x(int k) { return -100 + 40 * k; }      // LANE_X
+  static DEVI V monster(const int* s, int k, int sn, int cs) {
+    return view(fdiv(lane_x(k) * s[MD + k], DMAX), s[MD + k], sn, cs, 1);
+  }
+  static DEVI void reset(int* s, const Rng& g) {
+    s[TH] = 0;
+    s[COOL] = 0;
+    s[HEALTHF] = HEALTH;
+    s[TIC] = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      s[MD + k] = DMAX - g.rand(80 + k, STAGGER);
+      s[MHP + k] = 1;
+      s[MT + k] = 0;
+      s[MK + k] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < NF; ++j) s[FD + j] = 0;
+    s[ALIVE] = (1 << NM) - 1;
+    s[FACT] = 0;
+  }
+  static DEVI bool over(const int* s) { return s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng&) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = clampi(s[TH] + TURN * ((a == 2) - (a == 3)), -TH_MAX, TH_MAX);
+    const int cool = max(s[COOL] - 1, 0);
+    const bool fire = a == 1 && cool == 0;
+    s[COOL] = fire ? COOLDOWN : cool;
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+    int alive = s[ALIVE], act = s[FACT];
+    int key = BIG;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      const V v = monster(s, k, sn, cs);
+      const bool cand = ((alive >> k) & 1) && covers(v, (k & 1) ? SH_W : MON_W);
+      key = min(key, cand ? v.dz * 8 + k : BIG);
+    }
+    const bool hit = fire && key < BIG;
+    int reward = 0, biting = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      const bool shot = hit && (key & 7) == k;
+      s[MHP + k] -= shot;
+      const bool dead = shot && s[MHP + k] <= 0;
+      alive &= ~((dead ? 1 : 0) << k);
+      s[MT + k] = dead ? RESPAWN : s[MT + k];
+      s[MK + k] += dead;
+      reward += dead;
+      if ((alive >> k) & 1) {                    // melee walk to the player, shooters to their stand-off
+        s[MD + k] = max(s[MD + k] - 1, (k & 1) ? STANDOFF : 0);
+        biting += !(k & 1) && s[MD + k] == 0;
+      }
+    }
+    if (fmodi(s[TIC], BITE) == 0) s[HEALTHF] -= biting * DAMAGE;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {               // fireball j belongs to shooter 2 j + 1
+      const int k = 2 * j + 1;
+      if ((act >> j) & 1) {
+        s[FD + j] -= FSPEED;
+        if (s[FD + j] <= 0) {
+          s[HEALTHF] -= FDAMAGE;
+          act &= ~(1 << j);
+        }
+      }
+      const bool launch = ((alive >> k) & 1) && s[MD + k] == STANDOFF && !((act >> j) & 1) &&
+                          fmodi(s[TIC] + FPHASE * j, FIRE) == 0;
+      s[FD + j] = launch ? STANDOFF : s[FD + j];
+      act |= (launch ? 1 : 0) << j;
+    }
+#pragma unroll
+    for (int k = 0; k < NM; ++k)                 // dead slots come back at the far line, tougher
+      if (!((alive >> k) & 1)) {
+        s[MT + k] = max(s[MT + k] - 1, 0);
+        if (s[MT + k] == 0) {
+          alive |= 1 << k;
+          s[MD + k] = DMAX;
+          s[MHP + k] = min(1 + s[MK + k], HP_MAX);
+        }
+      }
+    s[ALIVE] = alive;
+    s[FACT] = act;
+    if (s[HEALTHF] <= 0) reward -= DEATH_PENALTY;
+    return reward;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      nav_object(r, NBACK + k, view((k - NP / 2) * POST_GAP, DMAX, sn, cs, 1), POST_W, 2 * FH, true);
+#pragma unroll
+    for (int k = 0; k < NM; ++k)
+      nav_object(r, NBACK + NP + k, monster(s, k, sn, cs), (k & 1) ? SH_W : MON_W, (k & 1) ? SH_H : MON_H,
+                 (s[ALIVE] >> k) & 1);
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      const int fd = max(s[FD + j], 0);
+      nav_object(r, NBACK + NP + NM + j, view(fdiv(lane_x(2 * j + 1) * fd, DMAX), fd, sn, cs, 1), FB_W, FB_H,
+                 (s[FACT] >> j) & 1, FB_LIFT);
+    }
+    rect(r, NBACK + NP + NM + NF, HUD_Y0 - 20, 74, 20, 12);      // the gun; unlimited ammo has no bar
+    hud(r, NBACK + NP + NM + NF + 1, s[HEALTHF], 0, false);
+  }
+};
+
+struct DoomHealthGathering : DoomNav {
+  static constexpr int LIVING = 1, DEATH_PENALTY = 100, TIMEOUT = 2100;
+  static constexpr int NK = 8, KIT0 = 4, NP = 8, ROOM = 96, KROOM = 88, SPEED = 4, TURN = 4;
+  static constexpr int ACID = 16, ACID_DMG = 8, SPAWN = 32, PICK = 12, HEAL = 25, HMAX = 100, HEALTH = 100;
+  static constexpr int KIT_W = 12, KIT_H = 12, POST_W = 12, KMULX = 37, KMULZ = 59;
+  enum { PX, PZ, TH, HEALTHF, TIC, KX, KZ = KX + NK, KACT = KZ + NK, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + NP + NK + 2;
+  static constexpr int SPAN = 2 * KROOM + 1;
+  // corners and wall middles, clockwise from (-ROOM, -ROOM)
+  static DEVI int post_x(int k) { return (k == 0 || k >= 6) ? -ROOM : (k == 1 || k == 5) ? 0 : ROOM; }
+  static DEVI int post_z(int k) { return k <= 2 ? -ROOM : (k == 3 || k == 7) ? 0 : ROOM; }
+  static DEVI void reset(int* s, const Rng& g) {
+    s[PX] = 0;
+    s[PZ] = 0;
+    s[TH] = g.rand(72, 256);
+    s[HEALTHF] = HEALTH;
+    s[TIC] = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      s[KX + k] = k < KIT0 ? g.rand(50 + k, SPAN) - KROOM : 0;
+      s[KZ + k] = k < KIT0 ? g.rand(60 + k, SPAN) - KROOM : 0;
+    }
+    s[KACT] = (1 << KIT0) - 1;
+  }
+  static DEVI bool over(const int* s) { return s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = fmodi(s[TH] + TURN * ((a == 2) - (a == 3)), 256);
+    const int fwd = a == 1 ? SPEED * U : 0;
+    s[PX] = clampi(s[PX] + fdiv(fwd * isin(s[TH]), 256), -ROOM * U, ROOM * U);
+    s[PZ] = clampi(s[PZ] + fdiv(fwd * icos(s[TH]), 256), -ROOM * U, ROOM * U);
+    const int wx = fdiv(s[PX], U), wz = fdiv(s[PZ], U);
+    int act = s[KACT], picked = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const bool pick = ((act >> k) & 1) && iabs(s[KX + k] - wx) <= PICK && iabs(s[KZ + k] - wz) <= PICK;
+      picked += pick;
+      act &= ~((pick ? 1 : 0) << k);
+    }
+    if (picked) s[HEALTHF] = min(s[HEALTHF] + HEAL * picked, HMAX);
+    if (fmodi(s[TIC], ACID) == 0) s[HEALTHF] -= ACID_DMG;
+    int empty = NK;                              // a new kit into the lowest empty slot
+#pragma unroll
+    for (int k = NK - 1; k >= 0; --k)
+      if (!((act >> k) & 1)) empty = k;
+    const bool spawn = fmodi(s[TIC], SPAWN) == 0;
+    const int nx = fmodi(g.rand(70, SPAN) + s[TIC] * KMULX, SPAN) - KROOM;
+    const int nz = fmodi(g.rand(71, SPAN) + s[TIC] * KMULZ, SPAN) - KROOM;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const bool here = spawn && k == empty;
+      s[KX + k] = here ? nx : s[KX + k];
+      s[KZ + k] = here ? nz : s[KZ + k];
+      act |= (here ? 1 : 0) << k;
+    }
+    s[KACT] = act;
+    return LIVING - (s[HEALTHF] <= 0 ? DEATH_PENALTY : 0);
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      nav_object(r, NBACK + k, view(post_x(k) * U - s[PX], post_z(k) * U - s[PZ], sn, cs, U), POST_W, 2 * FH, true);
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+      nav_object(r, NBACK + NP + k, view(s[KX + k] * U - s[PX], s[KZ + k] * U - s[PZ], sn, cs, U), KIT_W, KIT_H,
+                 (s[KACT] >> k) & 1);
+    hud(r, NBACK + NP + NK, s[HEALTHF], 0, false);
+  }
+};
+
+struct DoomCorridor : DoomNav {
+  static constexpr int DEATH_PENALTY = 100, TIMEOUT = 2100;
+  static constexpr int NE = 6, NPOST = 5, HALFW = 56, LEN = 1000, SPEED = 4, TURN = 2;
+  static constexpr int ENEMY_X = 40, EN_W = 24, EN_H = 40, RANGE = 160, EFIRE = 20, EPHASE = 3, EDMG = 8, EMISS = 4;
+  static constexpr int COOLDOWN = 8, AMMO = 26, HEALTH = 100, TOUCH = 24;
+  static constexpr int POST_W = 12, POST_GAP = 40, VEST_W = 16, VEST_H = 16;
+  enum { PX, PZ, TH, HEALTHF, AMMOF, COOL, TIC, WON, ALIVE, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + 2 * NPOST + 1 + NE + 4;
+  static DEVI int enemy_x(int i) { return (i & 1) ? ENEMY_X : -ENEMY_X; }
+  static DEVI int enemy_z(int i) { return i < 2 ? 250 : i < 4 ? 500 : 750; }      // GROUP_Z
+  static DEVI V enemy(const int* s, int i, int sn, int cs) {
+    return view(enemy_x(i) * U - s[PX], enemy_z(i) * U - s[PZ], sn, cs, U);
+  }
+  static DEVI void reset(int* s, const Rng&) {
+    s[PX] = 0;
+    s[PZ] = 0;
+    s[TH] = 0;
+    s[HEALTHF] = HEALTH;
+    s[AMMOF] = AMMO;
+    s[COOL] = 0;
+    s[TIC] = 0;
+    s[WON] = 0;
+    s[ALIVE] = (1 << NE) - 1;
+  }
+  static DEVI bool over(const int* s) { return s[WON] != 0 || s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = fmodi(s[TH] + TURN * ((a == 5) - (a == 6)), 256);
+    const int fwd = a == 4, side = (a == 2) - (a == 3);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+    const int old = fdiv(s[PZ], U);
+    s[PX] = clampi(s[PX] + fdiv(SPEED * U * (fwd * sn + side * cs), 256), -HALFW * U, HALFW * U);
+    s[PZ] = clampi(s[PZ] + fdiv(SPEED * U * (fwd * cs - side * sn), 256), 0, LEN * U);
+    const int wx = fdiv(s[PX], U), wz = fdiv(s[PZ], U);
+    int reward = wz - old;                       // whole-unit progress towards the vest
+    const int cool = max(s[COOL] - 1, 0);
+    const bool fire = a == 1 && cool == 0 && s[AMMOF] > 0;
+    s[COOL] = fire ? COOLDOWN : cool;
+    s[AMMOF] -= fire;
+    int alive = s[ALIVE];
+    int key = BIG;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+      const V v = enemy(s, i, sn, cs);
+      const bool cand = ((alive >> i) & 1) && covers(v, EN_W);
+      key = min(key, cand ? v.dz * 8 + i : BIG);
+    }
+    if (fire && key < BIG) alive &= ~(1 << (key & 7));
+    const int r90 = g.rand(90, EMISS);
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+      const bool shoot = ((alive >> i) & 1) && iabs(enemy_z(i) - wz) <= RANGE && fmodi(s[TIC] + EPHASE * i, EFIRE) == 0 &&
+                         fmodi(r90 + s[TIC] * 41 + i * 3, EMISS) != 0;
+      s[HEALTHF] -= shoot ? EDMG : 0;
+    }
+    s[ALIVE] = alive;
+    s[WON] = iabs(wx) <= TOUCH && LEN - wz <= TOUCH;
+    if (s[HEALTHF] <= 0) reward -= DEATH_PENALTY;
+    return reward;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+    const int base = fdiv(fdiv(s[PZ], U), POST_GAP) - 1;       // the window of posts slides with the player
+#pragma unroll
+    for (int side = 0; side < 2; ++side)
+#pragma unroll
+      for (int j = 0; j < NPOST; ++j) {
+        const int zj = (base + j) * POST_GAP;
+        nav_object(r, NBACK + side * NPOST + j,
+                   view((side ? HALFW : -HALFW) * U - s[PX], zj * U - s[PZ], sn, cs, U), POST_W, 2 * FH,
+                   zj >= 0 && zj <= LEN);
+      }
+    nav_object(r, NBACK + 2 * NPOST, view(-s[PX], LEN * U - s[PZ], sn, cs, U), VEST_W, VEST_H, true);
+#pragma unroll
+    for (int i = 0; i < NE; ++i)
+      nav_object(r, NBACK + 2 * NPOST + 1 + i, enemy(s, i, sn, cs), EN_W, EN_H, (s[ALIVE] >> i) & 1);
+    hud(r, NBACK + 2 * NPOST + 1 + NE, s[HEALTHF], s[AMMOF], true);
+  }
+};
+
 // --------------------------------------------------------------------------- driver
 // mode 0: agent step (actions), mode 1: reset_where(mask).  One thread per env.
 template <class G>
@@ -694,7 +1011,7 @@ static int launch(void* state, const void* actions, const void* mask, int mode, 
 }  // namespace games
 
 // game ids: 0 Breakout, 1 SpaceInvaders, 2 Alien, 3 MsPacman, 4 Centipede, 5 DoomBasic, 6 DoomDefendCenter,
-// 7 DoomTakeCover
+// 7 DoomTakeCover, 8 DoomDefendLine, 9 DoomHealthGathering, 10 DoomCorridor
 extern "C" int game_layout(int game, int* ns, int* nrects) {
   using namespace games;
   switch (game) {
@@ -706,6 +1023,9 @@ extern "C" int game_layout(int game, int* ns, int* nrects) {
     case 5: *ns = DoomBasic::NS; *nrects = DoomBasic::R; return 0;
     case 6: *ns = DoomDefendCenter::NS; *nrects = DoomDefendCenter::R; return 0;
     case 7: *ns = DoomTakeCover::NS; *nrects = DoomTakeCover::R; return 0;
+    case 8: *ns = DoomDefendLine::NS; *nrects = DoomDefendLine::R; return 0;
+    case 9: *ns = DoomHealthGathering::NS; *nrects = DoomHealthGathering::R; return 0;
+    case 10: *ns = DoomCorridor::NS; *nrects = DoomCorridor::R; return 0;
   }
   return -1;
 }
@@ -723,6 +1043,9 @@ extern "C" int launch_game_step(int game, void* state, const void* actions, cons
     case 5: return launch<DoomBasic>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 6: return launch<DoomDefendCenter>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 7: return launch<DoomTakeCover>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 8: return launch<DoomDefendLine>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 9: return launch<DoomHealthGathering>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 10: return launch<DoomCorridor>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
   }
   return -1;
 }

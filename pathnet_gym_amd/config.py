@@ -297,13 +297,23 @@ def preset(name: str) -> TrainConfig:
                            paths=64, envs_per_path=32, net=net, steps_per_task=DEVICE_TASK_STEPS,
                            ga=GAConfig(B=3, fitness="mean"),
                            a2c=A2CConfig(max_time_step=DEVICE_TASK_STEPS))
-    if name in ("doom3", "doom-basic", "doom_basic"):
-        # the synthetic first-person Doom scenarios (envs/doom_games.py): the "pong" network with a 4-way head
-        # (DoomBasic / DoomDefendCenter have 4 actions, DoomTakeCover 3), GA fitness and trunk scale of "atari4"
-        tasks = ["DoomBasic", "DoomDefendCenter", "DoomTakeCover"] if name == "doom3" else ["DoomBasic"]
+    doom_single = {"doom-basic": "DoomBasic", "doom_basic": "DoomBasic", "doom-corridor": "DoomCorridor",
+                   "doom-defend-line": "DoomDefendLine", "doom-health": "DoomHealthGathering"}
+    if name in ("doom3", "doom6") or name in doom_single:
+        # the synthetic first-person Doom scenarios (envs/doom_games.py): the "pong" network, GA fitness and trunk
+        # scale of "atari4".  "doom3" has a 4-way head (DoomBasic / DoomDefendCenter have 4 actions, DoomTakeCover
+        # 3); "doom6" is the six scenarios in LEVEL_NAMES order on the 7-way head DoomCorridor needs.
+        if name == "doom3":
+            tasks = ["DoomBasic", "DoomDefendCenter", "DoomTakeCover"]
+        elif name == "doom6":
+            tasks = ["DoomBasic", "DoomCorridor", "DoomDefendCenter", "DoomDefendLine", "DoomHealthGathering",
+                     "DoomTakeCover"]
+        else:
+            tasks = [doom_single[name]]
+        num_actions = 7 if "DoomCorridor" in tasks else 4
         net = PathNetConfig(L=5, M=10, N=4, input_shape=(160, 120, 4),
                             layers=reference_pixel_layers(5, fc=(256, 256)),
-                            trunk_scale="none", num_actions=4, num_tasks=len(tasks))
+                            trunk_scale="none", num_actions=num_actions, num_tasks=len(tasks))
         return TrainConfig(env=tasks[0], tasks=tasks, paths=64, envs_per_path=32, net=net,
                            steps_per_task=DEVICE_TASK_STEPS, ga=GAConfig(B=3, fitness="mean"),
                            a2c=A2CConfig(max_time_step=DEVICE_TASK_STEPS))

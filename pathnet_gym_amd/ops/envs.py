@@ -248,7 +248,8 @@ def rects_stack_push(geom: torch.Tensor, colors, bg, obs_in: torch.Tensor, obs_o
 
 # ------------------------------------------------------------------ synthetic Atari-style games (csrc/games.hip)
 GAME_IDS = {"Breakout": 0, "SpaceInvaders": 1, "Alien": 2, "MsPacman": 3, "Centipede": 4,
-            "DoomBasic": 5, "DoomDefendCenter": 6, "DoomTakeCover": 7}
+            "DoomBasic": 5, "DoomDefendCenter": 6, "DoomTakeCover": 7, "DoomDefendLine": 8,
+            "DoomHealthGathering": 9, "DoomCorridor": 10}
 
 
 def game_layout(game: str):

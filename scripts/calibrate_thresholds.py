@@ -180,10 +180,61 @@ def doom_take_cover_expert(env):
     return torch.stack(costs, 1).argmin(1)
 
 
+def doom_defend_line_expert(env):
+    """Shoot whenever the hit-scan rule would hit; otherwise turn to the most urgent living monster, the one with
+    the fewest tics left before it can hurt (shooters count from their stand-off, so they come first)."""
+    dx, _ = env.monsters_view()
+    urgency = torch.where(env.is_sh, env.md - env.STANDOFF, env.md)
+    urgency = torch.where(env.alive, urgency, torch.full_like(urgency, env.BIG))
+    tdx = dx.gather(1, urgency.argmin(1, keepdim=True)).squeeze(1)
+    a = torch.where(tdx > 0, 2, 3)                                             # TURN_RIGHT / TURN_LEFT
+    a = torch.where(env.aim() < env.BIG, torch.ones_like(a), a)                # ATTACK
+    return torch.where(env.alive.any(1), a, torch.zeros_like(a))
+
+
+def _steer(dx, dz, slack, forward, right, left):
+    """Walk to a point at view offset (dx, dz): forward when it is ahead within ``slack``, else turn to it."""
+    ahead = (dz > 0) & (dx.abs() <= slack)
+    return torch.where(ahead, forward, torch.where(dx >= 0, right, left))
+
+
+def doom_health_gathering_expert(env):
+    """Turn to the nearest kit (city-block distance) and walk; wait when there is none."""
+    from pathnet_gym_amd.envs.doom_games import U
+    rx, rz = env.kx * U - env.px[:, None], env.kz * U - env.pz[:, None]
+    dist = torch.where(env.kact, rx.abs() + rz.abs(), torch.full_like(rx, 1 << 30))
+    k = dist.argmin(1, keepdim=True)
+    dx, dz = env.view(rx, rz)
+    dx, dz = dx.gather(1, k).squeeze(1), dz.gather(1, k).squeeze(1)
+    a = _steer(dx, dz, torch.clamp(dz // 4, min=env.PICK - 4), 1, 2, 3)
+    return torch.where(env.kact.any(1), a, torch.zeros_like(a))
+
+
+def doom_corridor_expert(env):
+    """Advance to the vest; while a living enemy is within ``CLOSE`` (inside its range, and near enough to be
+    drawn and aimed at with the turn's step), turn onto it, side-step the last few units, and shoot when the
+    hit-scan rule would hit."""
+    from pathnet_gym_amd.envs.doom_games import U
+    CLOSE = 100
+    vdx, vdz = env.view(-env.px, env.LEN * U - env.pz)
+    go = _steer(vdx, vdz, torch.clamp(vdz // 8, min=8), 4, 5, 6)               # MOVE_FORWARD, TURN_RIGHT, TURN_LEFT
+    rz = (env.ez - (env.pz // U)[:, None]).abs()
+    threat = env.alive & (rz <= CLOSE)
+    k = torch.where(threat, rz * 8 + env.kidx, torch.full_like(rz, env.BIG)).argmin(1, keepdim=True)
+    dx, dz = env.enemies_view()
+    dx, dz = dx.gather(1, k).squeeze(1), dz.gather(1, k).squeeze(1)
+    turn = torch.where(dx >= 0, 5, 6)
+    strafe = torch.where(dx >= 0, 2, 3)                                        # MOVE_RIGHT / MOVE_LEFT
+    a = torch.where((dz <= 0) | (dx.abs() > 30), turn, strafe)
+    a = torch.where(env.aim() < env.BIG, torch.ones_like(a), a)                # ATTACK
+    return torch.where(threat.any(1) & (env.ammo > 0), a, go)
+
+
 EXPERTS = {"Pong": pong_expert, "Breakout": breakout_expert, "SpaceInvaders": invaders_expert,
            "Alien": alien_expert, "MsPacman": alien_expert, "Centipede": centipede_expert,
            "DoomBasic": doom_basic_expert, "DoomDefendCenter": doom_defend_center_expert,
-           "DoomTakeCover": doom_take_cover_expert}
+           "DoomTakeCover": doom_take_cover_expert, "DoomDefendLine": doom_defend_line_expert,
+           "DoomHealthGathering": doom_health_gathering_expert, "DoomCorridor": doom_corridor_expert}
 
 
 def play(game: str, policy: str, n: int, episodes: int, max_steps: int, device, seed: int = 7):
@@ -220,7 +271,8 @@ def play(game: str, policy: str, n: int, episodes: int, max_steps: int, device, 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="Pong,Breakout,SpaceInvaders,Alien,MsPacman,Centipede,"
-                                       "DoomBasic,DoomDefendCenter,DoomTakeCover")
+                                       "DoomBasic,DoomDefendCenter,DoomTakeCover,"
+                                       "DoomDefendLine,DoomHealthGathering,DoomCorridor")
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--max-steps", type=int, default=27000)
