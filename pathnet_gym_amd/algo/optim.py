@@ -9,8 +9,10 @@ Reference ``rmsprop_applier.py``:
   non-frozen tensors are applied even with zero gradient (rms decays).
 
 Here a "tensor" is a Segment of the flat buffer.  The torch path is the
-oracle; the HIP path is two launches (``segment_sqnorm`` + fused
-clip/apply that also refreshes the bf16 compute copy).
+oracle; the HIP path (``csrc/optim.hip`` ``launch_rmsprop``) is three
+launches: per-block squared norms, the non-finite flag, and the fused
+clip/apply.  The MFMA operand copies of the weights are refreshed
+separately, after the step (``launch_refresh_weights*``).
 """
 from __future__ import annotations
 
