@@ -15,9 +15,17 @@
 // TF layout) producing dx (into the trunk's feature gradient) and dh_{t-1}.  Weight
 // gradient: one split-R MFMA GEMM over all T*B rows after the reverse scan (LDS
 // transposed reads, fp32 atomics into the flat gradient), bias gradient fused.
+// Ordered weight gradient (deterministic=True, launch_lstm_wgrad_ord): the same operands, rounding, tile and
+// LDS staging, but the rows are cut into chunks of LORD_CHUNK rows (the chunk count depends on R alone), each
+// chunk's partial dK / db goes to its own slab of a caller-provided scratch buffer with plain stores, and
+// lstm_wgrad_ord_reduce_kernel adds the slabs in chunk order into the flat gradient (the scheme of
+// csrc/lstm_f32.hip).  No float atomics and no LDS atomics: one seed gives a bit-identical gradient run to run.
+// The forward, the pointwise backward and the backward GEMM have no atomics and serve both modes.
 #include "common.h"
 
 namespace lstmk {
+
+#define LORD_CHUNK 4096                           // ordered weight gradient: rows per partial slab
 
 DEVI float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 DEVI float tanh_f(float x) {
@@ -243,6 +251,99 @@ __global__ __launch_bounds__(256) void lstm_wgrad_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// ordered weight gradient, partial slabs.  grid ((F+H)/64, 4H/64, nchunks): lstm_wgrad_kernel's tile, staging and
+// MFMA loop over chunk blockIdx.z's LORD_CHUNK rows, walked 32 at a time in row order; the 64x64 partial dK is
+// stored to the chunk's slab.  The blockIdx.x == 0 workgroups also write the chunk's db (unrounded fp32 dz): thread
+// tid sums rows srow, srow + 32, ... of its 8 columns in row order, then column tid's 32 partials are added in
+// srow order.  Slab of chunk c: part + c * (KK*G4 + G4), dK [F+H][4H] then db [4H] (csrc/lstm_f32.hip's layout).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lstm_wgrad_ord_kernel(const bf16_t* __restrict__ xh,
+                                                             const float* __restrict__ dz,
+                                                             float* __restrict__ part, int F, int H, long R) {
+  constexpr int S = 64 + 8;
+  __shared__ __attribute__((aligned(16))) bf16_t Xs[32 * S];
+  __shared__ __attribute__((aligned(16))) bf16_t Gs[32 * S];
+  __shared__ float bred[32 * 64];
+  const int KK = F + H, G4 = 4 * H;
+  const int n0b = blockIdx.x * 64, p0b = blockIdx.y * 64;
+  const long r_beg = (long)blockIdx.z * LORD_CHUNK;
+  const long r_end = min(R, r_beg + LORD_CHUNK);
+  float* slab = part + (long)blockIdx.z * ((long)KK * G4 + G4);
+  const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+  const int grp = l >> 4, i16 = l & 15, q = i16 >> 2, pp = i16 & 3;
+  f4v acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) { acc[a][0] = {0.f, 0.f, 0.f, 0.f}; acc[a][1] = {0.f, 0.f, 0.f, 0.f}; }
+  float bpart[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int srow = tid >> 3, sc = (tid & 7) * 8;
+  const int mt0 = 2 * (w >> 1), nt0 = 2 * (w & 1);
+  for (long rb = r_beg; rb < r_end; rb += 32) {
+    const long r = rb + srow;
+    s8v xv = {0, 0, 0, 0, 0, 0, 0, 0}, gv8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r < r_end) {
+      xv = *reinterpret_cast<const s8v*>(xh + r * KK + n0b + sc);
+      const float4 g0 = *reinterpret_cast<const float4*>(dz + r * G4 + p0b + sc);
+      const float4 g1 = *reinterpret_cast<const float4*>(dz + r * G4 + p0b + sc + 4);
+      const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+      for (int c = 0; c < 8; ++c) bpart[c] += gg[c];
+      gv8 = f32x8_to_bf16(gg);
+    }
+    *reinterpret_cast<s8v*>(Xs + srow * S + sc) = xv;
+    *reinterpret_cast<s8v*>(Gs + srow * S + sc) = gv8;
+    __syncthreads();
+    s8v af[2], bf[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const s4v v0 = lds_tr16(Xs + (8 * grp + q) * S + (mt0 + i) * 16 + 4 * pp);
+      const s4v v1 = lds_tr16(Xs + (8 * grp + 4 + q) * S + (mt0 + i) * 16 + 4 * pp);
+      af[i] = (s8v){v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+      const s4v u0 = lds_tr16(Gs + (8 * grp + q) * S + (nt0 + i) * 16 + 4 * pp);
+      const s4v u1 = lds_tr16(Gs + (8 * grp + 4 + q) * S + (nt0 + i) * 16 + 4 * pp);
+      bf[i] = (s8v){u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma16(af[i], bf[jj], acc[i][jj]);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0b + (mt0 + i) * 16 + 4 * grp + r;
+        const int p = p0b + (nt0 + jj) * 16 + i16;
+        slab[(long)n * G4 + p] = acc[i][jj][r];
+      }
+  if (blockIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) bred[srow * 64 + sc + c] = bpart[c];
+    __syncthreads();
+    if (tid < 64) {
+      float s = 0.f;
+      for (int rr = 0; rr < 32; ++rr) s += bred[rr * 64 + tid];
+      slab[(long)KK * G4 + p0b + tid] = s;
+    }
+  }
+}
+
+// grad[k_off + i] += sum_c slab_c.dK[i], grad[b_off + p] += sum_c slab_c.db[p], the slabs summed in chunk order
+__global__ __launch_bounds__(256) void lstm_wgrad_ord_reduce_kernel(const float* __restrict__ part,
+                                                                    float* __restrict__ grad, long k_off,
+                                                                    long b_off, long n_k, int G4, int nchunks) {
+  const long n_el = n_k + G4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_el; i += (long)gridDim.x * 256) {
+    float s = 0.f;
+    for (int c = 0; c < nchunks; ++c) s += part[(long)c * n_el + i];
+    const long o = i < n_k ? k_off + i : b_off + (i - n_k);
+    grad[o] += s;
+  }
+}
+
 // bf16 compute copies of the fp32 master kernel: KpT (permuted K^T, forward) and Kb (TF layout, backward)
 __global__ void lstm_refresh_kernel(const float* __restrict__ flat, long k_off, int F, int H,
                                     bf16_t* __restrict__ KpT, bf16_t* __restrict__ Kb) {
@@ -310,6 +411,29 @@ int launch_lstm_wgrad(const void* xh, const float* dz, float* grad, long k_off, 
   if (F % 64 != 0 || H % 64 != 0 || rows_per_chunk % 32 != 0) return -1;
   dim3 grid((F + H) / 64, (4 * H) / 64, (unsigned)((R + rows_per_chunk - 1) / rows_per_chunk));
   lstm_wgrad_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)xh, dz, grad, k_off, b_off, F, H, R, rows_per_chunk);
+  return (int)hipGetLastError();
+}
+
+// rows per partial slab of the ordered weight gradient, and the scratch floats launch_lstm_wgrad_ord needs for R rows
+int lstm_wgrad_ord_chunk_rows() { return LORD_CHUNK; }
+long lstm_wgrad_ord_part_numel(int F, int H, long R) {
+  if (F <= 0 || H <= 0 || R <= 0) return 0;
+  const long nch = (R + LORD_CHUNK - 1) / LORD_CHUNK;
+  return nch * ((long)(F + H) * 4 * H + 4L * H);
+}
+
+int launch_lstm_wgrad_ord(const void* xh, const float* dz, float* grad, float* part, long k_off, long b_off, int F,
+                          int H, long R, hipStream_t stream) {
+  if (F <= 0 || H <= 0 || R <= 0 || k_off < 0 || b_off < 0 || !part) return -22;
+  if (F % 64 != 0 || H % 64 != 0) return -1;
+  const long nch = (R + LORD_CHUNK - 1) / LORD_CHUNK;
+  if (nch > 65535) return -1;
+  const int G4 = 4 * H;
+  const long n_k = (long)(F + H) * G4;
+  dim3 grid((F + H) / 64, G4 / 64, (unsigned)nch);
+  lstm_wgrad_ord_kernel<<<grid, 256, 0, stream>>>((const bf16_t*)xh, dz, part, F, H, R);
+  lstm_wgrad_ord_reduce_kernel<<<(unsigned)min((n_k + G4 + 255) / 256, 2048L), 256, 0, stream>>>(
+      part, grad, k_off, b_off, n_k, G4, (int)nch);
   return (int)hipGetLastError();
 }
 

@@ -82,6 +82,9 @@ _SIGS = {
     "launch_lstm_bwd_point": [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P],
     "launch_lstm_bwd_gemm": [P, P, P, c_int, P, c_int, c_int, c_int, P],
     "launch_lstm_wgrad": [P, P, P, c_long, c_long, c_int, c_int, c_long, c_int, P],
+    "launch_lstm_wgrad_ord": [P, P, P, P, c_long, c_long, c_int, c_int, c_long, P],
+    "lstm_wgrad_ord_part_numel": [c_int, c_int, c_long],
+    "lstm_wgrad_ord_chunk_rows": [],
     "launch_lstm_refresh": [P, c_long, c_int, c_int, P, P, P],
     "launch_lstm_carry": [P, P, P, P, P, c_int, c_int, P],
     "launch_lstm_fwd_x3": [P, c_int, P, P, P, P, P, c_long, P, P, P, P, P, P, c_int, c_int, c_int, P],

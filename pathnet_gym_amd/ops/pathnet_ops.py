@@ -279,18 +279,23 @@ class HipPathNet:
         # hi+lo pairs, fp32 state: the reference's default network at its precision) or, in fp32, csrc/lstm_f32.hip
         # (fp32 operands read from the flat master, fixed-order reductions: no operand copies, a partial-slab
         # scratch for the weight gradient).  PATHNET_F32_LSTM=0 keeps the hybrid autograd LSTM for fp32 (A/B runs).
-        # The bf16 engine with deterministic=True keeps the hybrid path too: its features are bf16 and an ordered
-        # bf16 cell is out of scope.
+        # The bf16 engine with deterministic=True runs the bf16 cell of csrc/lstm.hip with the ordered weight gradient
+        # (ord: launch_lstm_wgrad_ord, partial slabs added in chunk order; the cell's other kernels have no atomics);
+        # PATHNET_BF16_DET_LSTM=0 keeps the hybrid autograd LSTM there (A/B runs).
         self.lstm = None
         f32_lstm = self.f32 and os.environ.get("PATHNET_F32_LSTM", "1") != "0"
-        if cfg.use_lstm and (f32_lstm or not self.deterministic):
+        ord_lstm = (self.deterministic and not self.f32
+                    and os.environ.get("PATHNET_BF16_DET_LSTM", "1") != "0")
+        if cfg.use_lstm and (f32_lstm or ord_lstm or not self.deterministic):
             ls = lay.lstm
             F, H = ls["din"], ls["H"]
             if F % 64 == 0 and H % 64 == 0 and f32_lstm:
-                self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=False, f32=True, part=None)
+                self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=False, f32=True, ord=False,
+                                 part=None)
             elif F % 64 == 0 and H % 64 == 0:
                 pl = (2,) if self.x3 else ()
                 self.lstm = dict(F=F, H=H, k_off=ls["kernel"], b_off=ls["bias"], x3=self.x3, f32=False,
+                                 ord=ord_lstm, part=None,
                                  KpT=torch.zeros(pl + (4 * H, F + H), dtype=torch.float16 if self.x3 else torch.bfloat16,
                                                  device=dev),
                                  Kb=torch.zeros(pl + (F + H, 4 * H), dtype=torch.float16 if self.x3 else torch.bfloat16,
@@ -452,17 +457,19 @@ class HipPathNet:
 
     def lstm_prepare(self, T: int, B: int = 0):
         """Buffers sized by the rollout, allocated before any graph capture.  fp32x: the G16 amax slots of a T-step
-        rollout; fp32: the weight gradient's partial slabs for the T * B rows of a rollout of B agents
-        (csrc/lstm_f32.hip; without B they are allocated by the first lstm_wgrad, which must then run eagerly)."""
+        rollout; fp32 and deterministic bf16: the weight gradient's partial slabs for the T * B rows of a rollout of
+        B agents (csrc/lstm_f32.hip, csrc/lstm.hip launch_lstm_wgrad_ord; without B they are allocated by the first
+        lstm_wgrad, which must then run eagerly)."""
         ls = self.lstm
-        if ls is not None and ls["f32"] and B > 0:
+        if ls is not None and (ls["f32"] or ls["ord"]) and B > 0:
             self._lstm_part(T * B)
         if ls is not None and ls["x3"] and ls["amax"].numel() < T + 1:
             ls["amax"] = torch.zeros(T + 1, dtype=torch.float32, device=ls["amax"].device)
 
     def _lstm_part(self, R: int) -> torch.Tensor:
         ls = self.lstm
-        n = _lib.lib().lstm_wgrad_f32_part_numel(ls["F"], ls["H"], R)
+        numel = _lib.lib().lstm_wgrad_f32_part_numel if ls["f32"] else _lib.lib().lstm_wgrad_ord_part_numel
+        n = numel(ls["F"], ls["H"], R)
         if ls["part"] is None or ls["part"].numel() < n:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("LSTM weight-gradient partials first needed inside a graph capture")
@@ -529,13 +536,20 @@ class HipPathNet:
                   dh_prev.data_ptr(), ls["F"], ls["H"], B, st)
 
     def lstm_wgrad(self, xh, dz, grad_flat, rows_per_chunk: int = 2048):
-        """fp32: fixed row chunks (csrc/lstm_f32.hip LF32_CHUNK) and ordered sums; rows_per_chunk is not used."""
+        """fp32 and deterministic bf16: fixed row chunks (csrc/lstm_f32.hip LF32_CHUNK, csrc/lstm.hip LORD_CHUNK) and
+        ordered sums; rows_per_chunk is not used."""
         ls = self.lstm
         R = xh.numel() // (ls["F"] + ls["H"])
         if ls["f32"]:
             _lib.check(xh, torch.float32, name="xh")
             _lib.check(dz, torch.float32, numel=R * 4 * ls["H"], name="dz")
             _lib.call("launch_lstm_wgrad_f32", xh.data_ptr(), dz.data_ptr(), grad_flat.data_ptr(),
+                      self._lstm_part(R).data_ptr(), ls["k_off"], ls["b_off"], ls["F"], ls["H"], R, _lib.stream())
+            return
+        if ls["ord"]:
+            _lib.check(xh, torch.bfloat16, name="xh")
+            _lib.check(dz, torch.float32, numel=R * 4 * ls["H"], name="dz")
+            _lib.call("launch_lstm_wgrad_ord", xh.data_ptr(), dz.data_ptr(), grad_flat.data_ptr(),
                       self._lstm_part(R).data_ptr(), ls["k_off"], ls["b_off"], ls["F"], ls["H"], R, _lib.stream())
             return
         if ls["x3"]:

@@ -157,8 +157,9 @@ class HipEngine:
         # all-reduce (parallel/comm.py exchange_async_split)
         self.split = False
         # LSTM nets: fused HIP LSTM cell (csrc/lstm.hip; fp32x: csrc/lstm_x3.hip; fp32: csrc/lstm_f32.hip) when the
-        # widths are multiples of 64; otherwise, and in the bf16 engine's deterministic mode, the hybrid path (HIP
-        # trunk + autograd LSTM/heads/loss, dL/dfeat fed back to the HIP trunk backward: eager, never captured)
+        # widths are multiples of 64, the bf16 engine's deterministic mode included (ordered weight gradient,
+        # launch_lstm_wgrad_ord; grads[-1] is fp32 there); otherwise the hybrid path (HIP trunk + autograd
+        # LSTM/heads/loss, dL/dfeat fed back to the HIP trunk backward: eager, never captured)
         self.lstm_hip = hp.lstm is not None
         self.hybrid = bool(model.cfg.use_lstm) and not self.lstm_hip
         self.lstm_state = model.init_state(B) if self.hybrid else None
