@@ -215,11 +215,12 @@ __global__ __launch_bounds__(256) void lstm_bwd_point_x3_kernel(
   float am = 0.f;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < (long)B * H; idx += (long)gridDim.x * 256) {
     const int row = (int)(idx / H), u = (int)(idx - (long)row * H);
-    const float kt = (done_t && done_t[row]) ? 0.f : 1.f;
+    // a select, as in csrc/lstm.hip: whatever an ended episode's row holds upstream (NaN, inf) is never read
+    const bool kt = !(done_t && done_t[row]);
     float dh = dh_heads[idx];
     float dc = 0.f;
-    if (dh_rec) dh += kt * dh_rec[idx];
-    if (dc_rec) dc = kt * dc_rec[idx];
+    if (dh_rec && kt) dh += dh_rec[idx];
+    if (dc_rec && kt) dc = dc_rec[idx];
     const float* gr = gates + (long)row * 4 * H;
     const float si = gr[u], tj = gr[H + u], sf = gr[2 * H + u], so = gr[3 * H + u];
     const float c = c_t[idx];
@@ -471,6 +472,7 @@ int launch_lstm_wgrad_x3(const float* xh, const float* dz, float* grad, long k_o
 int launch_lstm_refresh_x3(const float* flat, long k_off, int F, int H, void* KpT2, void* Kb2, void* status,
                            hipStream_t stream) {
   if (F <= 0 || H <= 0 || k_off < 0) return -22;
+  if (F % 64 != 0 || H % 64 != 0) return -1;     // the tile-major permutation leaves KpT2's 4H rows when H % 16 != 0
   const long n = (long)(F + H) * 4 * H;
   lstm_refresh_x3_kernel<<<(unsigned)((n + 255) / 256), 256, 0, stream>>>(flat, k_off, F, H, (uint16_t*)KpT2,
                                                                           (uint16_t*)Kb2, (uint32_t*)status);
