@@ -693,3 +693,56 @@ extern "C" int launch_fitness_update(const void* dones, const float* epret, int 
   fitness_counters_kernel<<<1, 64, 0, stream>>>(path_part, T, P, E, counters);
   return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// episode ledger of a forward-only evaluation (runtime/evaluator.py): after a chunk of T steps, env b < nvalid
+// records the return and the 1-based global end step of every episode it finished, in step order, until it holds
+// `quota` of them or the evaluation's clock reaches max_steps.  clock (the steps played before this chunk) lives on
+// the device so that a captured chunk can be replayed; pending = envs still short of their quota, the 4 bytes the
+// host reads to decide whether to stop.  One workgroup: each thread walks its envs' T steps in order (no atomics,
+// nothing depends on arrival order), the pending count is reduced through LDS in thread order.  Only
+// ret/endstep[b, cnt[b] before .. cnt[b] after) are written; envs >= nvalid are never touched.
+// algo/evaluate.py ledger_ref is the same rule in numpy.
+// ---------------------------------------------------------------------------
+#define LEDGER_THREADS 256
+__global__ __launch_bounds__(LEDGER_THREADS) void eval_ledger_kernel(
+    const uint8_t* __restrict__ dones, const float* __restrict__ epret, int T, int B, int nvalid, int quota,
+    long long max_steps, int* __restrict__ cnt, float* __restrict__ ret, int* __restrict__ endstep,
+    long long* __restrict__ clock, int* __restrict__ pending) {
+  __shared__ int red[LEDGER_THREADS];
+  const int tid = threadIdx.x;
+  const long long clk = clock[0];
+  int short_of = 0;
+  for (int b = tid; b < nvalid; b += LEDGER_THREADS) {
+    const int c0 = cnt[b];
+    int c = c0;
+    if (c >= 0) {               // a negative count is never indexed with
+      for (int t = 0; t < T && c < quota && clk + t < max_steps; ++t) {
+        const long i = (long)t * B + b;
+        if (dones[i]) {
+          ret[(long)b * quota + c] = epret[i];
+          endstep[(long)b * quota + c] = (int)(clk + t + 1);
+          ++c;
+        }
+      }
+      if (c != c0) cnt[b] = c;
+    }
+    short_of += c < quota ? 1 : 0;
+  }
+  red[tid] = short_of;
+  __syncthreads();              // also: every thread has read clock before thread 0 advances it
+  if (tid != 0) return;
+  int n = 0;
+  for (int i = 0; i < LEDGER_THREADS; ++i) n += red[i];
+  pending[0] = n;
+  clock[0] = clk + T;
+}
+
+extern "C" int launch_eval_ledger(const void* dones, const float* epret, int T, int B, int nvalid, int quota,
+                                  long max_steps, int* cnt, float* ret, int* endstep, long long* clock,
+                                  int* pending, hipStream_t stream) {
+  if (T <= 0 || B <= 0 || quota <= 0 || nvalid < 0 || nvalid > B) return -1;
+  eval_ledger_kernel<<<1, LEDGER_THREADS, 0, stream>>>((const uint8_t*)dones, epret, T, B, nvalid, quota,
+                                                       (long long)max_steps, cnt, ret, endstep, clock, pending);
+  return (int)hipGetLastError();
+}

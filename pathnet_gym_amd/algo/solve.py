@@ -49,7 +49,13 @@ class SolveTracker:
     solve or the task horizon).  ``record()`` is the JSON summary."""
 
     def __init__(self, tr, confirm_threshold: float = 17.0, confirm_episodes: int = 64, eval_seed: Optional[int] = None,
-                 max_eval_steps: int = 30000, wall_s: float = math.inf, log=None):
+                 max_eval_steps: int = 30000, wall_s: float = math.inf, log=None, confirm_backend: str = "torch",
+                 confirm_compute_dtype: Optional[str] = None):
+        # confirm_backend: evaluate_path's backend for the held-out check.  "torch" (default) is the fp32 PyTorch
+        # forward, independent of the HIP kernels that produced the fitness; "hip" / "auto" run the forward-only HIP
+        # engine (runtime/evaluator.py) at confirm_compute_dtype (default: the trainer's own precision)
+        self.confirm_backend = confirm_backend
+        self.confirm_compute_dtype = confirm_compute_dtype
         self.tr = tr
         cfg = tr.cfg
         self.task = tr.task_idx
@@ -86,7 +92,8 @@ class SolveTracker:
         if ctx.is_main or not ctx.enabled:
             ev = evaluate_path(tr.cfg.net, tr.model.store.flat, expr, self.env_id, task=tr.model.task,
                                episodes=self.confirm_episodes, seed=self.eval_seed, device=tr.device,
-                               frameskip=tr.cfg.frameskip, gray=tr.cfg.gray, max_steps=self.max_eval_steps)
+                               frameskip=tr.cfg.frameskip, gray=tr.cfg.gray, max_steps=self.max_eval_steps,
+                               **self._backend_kw())
         else:
             ev = {"mean": -math.inf}
         m = ev["mean"] if math.isfinite(ev["mean"]) else -math.inf
@@ -95,6 +102,13 @@ class SolveTracker:
         ev["seconds"] = round(time.time() - t, 1)
         self.eval_s += time.time() - t
         return ev
+
+    def _backend_kw(self) -> dict:
+        """evaluate_path's backend arguments; none for the default, so the call is the one it always was."""
+        if self.confirm_backend == "torch":
+            return {}
+        dt = self.confirm_compute_dtype or getattr(self.tr, "compute_dtype", None)
+        return {"backend": self.confirm_backend, "compute_dtype": dt}
 
     def observe(self, st) -> bool:
         tr = self.tr
@@ -132,7 +146,9 @@ class SolveTracker:
         tr = self.tr
         s = self.solved
         return {"criterion": CRITERION, "threshold": self.threshold, "confirm_threshold": self.confirm_threshold,
-                "confirm_episodes": self.confirm_episodes, "confirm_policy": "sampled, fp32 PyTorch forward",
+                "confirm_episodes": self.confirm_episodes,
+                "confirm_policy": ("sampled, fp32 PyTorch forward" if self.confirm_backend == "torch"
+                                   else f"sampled, backend {self.confirm_backend}"),
                 "eval_seed": self.eval_seed, "horizon_frames": self.horizon, "stopped": self.stopped,
                 "solved": s is not None, "generations_to_solve": s and s["generation"],
                 "updates_to_solve": s and s["updates"], "frames_to_solve": s and s["frames"],

@@ -117,6 +117,11 @@ def build_parser():
     e.add_argument("--checkpoint", required=True)
     e.add_argument("--episodes", type=int, default=1)
     e.add_argument("--max_steps", type=int, default=2000)
+    # --backend / --compute_dtype / --seed (above) select the evaluation backend here: torch (default: the PyTorch
+    # oracle stepped from Python) | hip (the forward-only HIP engine, runtime/evaluator.py) | auto
+    e.add_argument("--device", default="cpu", help="device of the torch backend; the hip backend runs on it when it "
+                                                   "is a GPU, else on the current GPU")
+    e.add_argument("--sample", action="store_true", help="sample the policy (seeded) instead of playing the argmax")
 
     v = sub.add_parser("visualize")
     v.add_argument("--checkpoint", required=True)
@@ -284,7 +289,15 @@ def cmd_train(a):
 def cmd_eval(a):
     from .algo.evaluate import evaluate_checkpoint
     cfg = config_from_args(a)
-    res = evaluate_checkpoint(cfg, a.checkpoint, episodes=a.episodes, max_steps=a.max_steps)
+    backend = a.backend or "torch"
+    if backend in ("auto", "hip"):
+        import torch
+        if torch.cuda.is_available():
+            from . import _build
+            _build.build()
+    res = evaluate_checkpoint(cfg, a.checkpoint, episodes=a.episodes, max_steps=a.max_steps, device=a.device,
+                              backend=backend, compute_dtype=a.compute_dtype, sample=a.sample,
+                              seed=12345 if a.seed is None else a.seed)
     print(json.dumps(res))
 
 

@@ -44,6 +44,7 @@ _SIGS = {
                         P, P, P, P],
     "launch_heads_bwd": [P, c_int, P, P, c_int, c_int, P, c_long, c_long, c_long, c_long, P, P, P],
     "launch_fitness_update": [P, P, c_int, c_int, c_int, P, P, P, P, c_int, P, P],
+    "launch_eval_ledger": [P, P, c_int, c_int, c_int, c_int, c_long, P, P, P, P, P, P],
     "launch_rmsprop": [P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_float, c_float, c_float, c_float, P],
     "launch_refresh_weights": [P, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "launch_pong_step": [P, P, P, c_int, P, P, P, P, P, P, c_int, c_uint, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -53,7 +53,10 @@ def loss_scale(cfg) -> float:
 
 
 class HipEngine:
-    def __init__(self, model, env, cfg, opt, seed: int = 1, row_base: int = 0):
+    def __init__(self, model, env, cfg, opt, seed: int = 1, row_base: int = 0, forward_only: bool = False):
+        # forward_only (runtime/evaluator.py): the rollout buffers and step helpers only -- no gradient buffers, no
+        # optimizer tables, no LSTM backward state; ``opt`` may be None and update() is not available
+        self.forward_only = bool(forward_only)
         self.model = model
         self.hip = model.hip
         self.env = env
@@ -105,12 +108,14 @@ class HipEngine:
         self.acts, self.bits, self.bits_rows, self.grads = [], [], [], []
         # conv-layer output gradients kept in bf16 where the specialised dgrad / wgrad kernels take them
         # (grads[0] is 1.5 GB and grads[1] 0.3 GB in fp32 at the bench shape)
-        bf16_grads = hp.grad_bf16_layers(self.ring)
+        bf16_grads = set() if self.forward_only else hp.grad_bf16_layers(self.ring)
         for l, g in enumerate(hp.geoms):
             self.acts.append(hp.alloc_act(l, (T + 1, B, g.out_feat)))
             b, rows = hp.alloc_bits(l, T + 1, B)
             self.bits.append(b)
             self.bits_rows.append(rows)
+            if self.forward_only:
+                continue
             self.grads.append(torch.zeros(T * B, g.out_feat, dtype=torch.bfloat16 if l in bf16_grads else torch.float32,
                                           device=dev))
         self.logits = torch.zeros(T + 1, B, A, device=dev)
@@ -119,10 +124,11 @@ class HipEngine:
         self.rewards = torch.zeros(T, B, device=dev)
         self.dones = torch.zeros(T, B, dtype=torch.uint8, device=dev)
         self.epret = torch.zeros(T, B, device=dev)
-        self.dlogits = torch.zeros(T, B, A, device=dev)
-        self.dvalue = torch.zeros(T, B, device=dev)
-        self.stats = torch.zeros(4, device=dev)          # a2c_grad: loss_pi, loss_v, entropy sum
-        self.grad_flat = torch.zeros_like(model.store.flat, requires_grad=False)
+        if not self.forward_only:
+            self.dlogits = torch.zeros(T, B, A, device=dev)
+            self.dvalue = torch.zeros(T, B, device=dev)
+            self.stats = torch.zeros(4, device=dev)          # a2c_grad: loss_pi, loss_v, entropy sum
+            self.grad_flat = torch.zeros_like(model.store.flat, requires_grad=False)
         self.fitness = torch.full((P,), -1000.0, device=dev)
         # windowed fitness (GAConfig.fitness == "mean"): episodes / return sum since the path's last tournament
         self.fit_window = cfg.ga.window_for(E)
@@ -148,7 +154,8 @@ class HipEngine:
         # end of the first layer's parameters (the overlapped exchange's second bucket, runtime/engine.py split)
         self._l0_end = max((s.offset + s.numel for s in model.store.layout.segments if s.layer == 0), default=0)
         # optimizer block table (segments split into <= 8192-element blocks)
-        self._build_opt_tables()
+        if not self.forward_only:
+            self._build_opt_tables()
         self.g_rollout = None
         self.g_opt = None
         self.ga_dev = None
@@ -166,9 +173,10 @@ class HipEngine:
         if self.lstm_hip:
             F, H = hp.lstm["F"], hp.lstm["H"]
             ldt = hp.lstm_dtype                  # bf16 (bf16 engine) or fp32 (fp32x and fp32 engines)
-            hp.lstm_prepare(T, B)
+            hp.lstm_prepare(T, 0 if self.forward_only else B)
             self.hst = torch.zeros(T + 2, B, H, dtype=ldt, device=dev)   # slot t = state entering step t
             self.cst = torch.zeros(T + 2, B, H, device=dev)
+        if self.lstm_hip and not self.forward_only:
             self.gates = torch.zeros(T, B, 4 * H, device=dev)
             self.xh = torch.zeros(T, B, F + H, dtype=ldt, device=dev)
             self.dz = torch.zeros(T, B, 4 * H, device=dev)
@@ -181,7 +189,8 @@ class HipEngine:
         # the heads + sampling of rollout steps 0..T-1 folded into the env step (frame-ring Pong, fp32 features):
         # one launch per step less (csrc/envs.hip pong_step_kernel HEADS)
         self.fuse_env_heads = (self.ring and getattr(env, "ring_heads", False) and hp.feat_dtype == torch.float32
-                               and not self.lstm_hip and not self.hybrid and self.env_graph_safe
+                               and not self.forward_only and not self.lstm_hip and not self.hybrid
+                               and self.env_graph_safe
                                and model.cfg.num_actions <= 8 and hp.geoms[-1].out_feat == 256
                                and os.environ.get("PATHNET_FUSE_ENV_HEADS", "1") != "0")
         self.auto_group_max_paths = int(os.environ.get("PATHNET_AUTO_GROUP_MAX_PATHS", "0"))
@@ -473,7 +482,7 @@ class HipEngine:
         if self.lstm_hip:
             # state entering step t: slot t, reset where the previous step ended an episode
             # (slot 0 is pre-masked by the carry at the end of the previous update)
-            last = t >= self.T
+            last = t >= self.T or self.forward_only       # nothing saved for a backward
             hp.lstm_fwd(feat, self.hst[t], self.cst[t], self.dones[t - 1] if t > 0 else None, self.hst[t + 1],
                         self.cst[t + 1], None if last else self.gates[t], None if last else self.xh[t])
             feat = self.hst[t + 1]
@@ -576,6 +585,31 @@ class HipEngine:
                          self.grads[L - 1], task=self.model.task)
         self._layer_bwd_all(T, 1 if part == "head" else 0)
         hp.fx_end(self.grad_flat, self._l0_end if part == "head" else 0)
+
+    def _rollout_only_body(self, greedy: bool = False):
+        """Forward-only rollout (runtime/evaluator.py): T x [trunk -> (LSTM cell) -> heads, argmax or sampled -> env
+        step] through the same step helpers as the training rollout -- no bootstrap forward, no fitness update, no
+        backward.  The env step's heads-fused launch has no greedy argument and is never taken here."""
+        if self.hybrid:
+            raise NotImplementedError("forward-only rollout: the hybrid (autograd) LSTM is not supported")
+        for t in range(self.T):
+            self._forward_step(t, greedy=greedy)
+            self._env_step(t)
+
+    def _carry_body(self):
+        """What a forward-only rollout hands to the next one, the optimizer body's carry without the optimizer: the
+        LSTM state (zeroed where the last step ended an episode), the frame ring's last four planes and first valid
+        channels (the modular ring and the observation double buffer need no copy), and the sampling counter."""
+        T = self.T
+        if self.lstm_hip:
+            self.hip.lstm_carry(self.hst[T], self.cst[T], self.dones[T - 1], self.hst[0], self.cst[0])
+        if self.ring and not self.ring_mod:
+            f64 = self.frames.view(torch.int64) if self.HW % 8 == 0 else self.frames
+            src = f64[:, T:T + 4]
+            f64[:, 0:4].copy_(src if T >= 4 else src.clone())   # T < 4: the slot ranges overlap
+        if self.ring:
+            self.fc[0].copy_(self.fc[T])
+        self.ctr.add_(1)
 
     def _rollout_split(self):
         """The rollout as independent per-path-group chains (forward -> sample -> env step, T times, then the
@@ -737,6 +771,8 @@ class HipEngine:
             self.lstm_state = (h.clone(), c.clone())
 
     def _optimizer_body(self):
+        # the carry below (LSTM state, ring planes, fc row, counter) has a forward-only twin, _carry_body: a change
+        # to what one rollout hands to the next belongs in both
         if self.lstm_hip:
             T = self.T
             self.hip.lstm_carry(self.hst[T], self.cst[T], self.dones[T - 1], self.hst[0], self.cst[0])

@@ -72,7 +72,9 @@ def greedy_eval(tr, ti, name, args, dev, sample=False, flat=None):
     m.set_paths(np.repeat(tr.task_paths[ti][None], n, axis=0))
     m.task = ti
     r = evaluate_model(m, name, episodes=1, max_steps=args.eval_steps, device=dev,
-                       frameskip=tr.cfg.frameskip, gray=tr.cfg.gray, sample=sample)
+                       frameskip=tr.cfg.frameskip, gray=tr.cfg.gray, sample=sample,
+                       **({} if args.eval_backend == "torch" else
+                          {"backend": args.eval_backend, "compute_dtype": getattr(tr, "compute_dtype", None)}))
     r = [x for x in r if math.isfinite(x)]
     return float(np.mean(r)) if r else None
 
@@ -135,6 +137,9 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--eval-episodes", type=int, default=4)
     ap.add_argument("--eval-steps", type=int, default=6000)
+    ap.add_argument("--eval_backend", default="torch", choices=["torch", "hip", "auto"],
+                    help="forgetting check: the PyTorch oracle with the torch env (default) or the forward-only HIP "
+                         "engine at the trainer's precision (runtime/evaluator.py)")
     ap.add_argument("--report-every", type=float, default=20.0)
     ap.add_argument("--control", action="store_true", help="also train tasks >= 2 from scratch (transfer control)")
     ap.add_argument("--stop-after-solve", type=float, default=None,

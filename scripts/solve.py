@@ -74,6 +74,9 @@ def main():
     ap.add_argument("--confirm", type=float, default=17.0,
                     help="held-out mean return that confirms a solve candidate (algo/solve.py)")
     ap.add_argument("--confirm-episodes", type=int, default=64, help="fresh episodes of the held-out confirmation")
+    ap.add_argument("--confirm_backend", default="torch", choices=["torch", "hip", "auto"],
+                    help="held-out confirmation: the fp32 PyTorch forward (default, independent of the HIP kernels) or "
+                         "the forward-only HIP engine at the trainer's precision (runtime/evaluator.py)")
     args = ap.parse_args()
 
     import torch
@@ -176,7 +179,8 @@ def main():
                 curve.flush()
 
     trk = SolveTracker(tr, confirm_threshold=args.confirm, confirm_episodes=args.confirm_episodes,
-                       wall_s=args.minutes * 60 - prior["seconds"], log=log_candidate)
+                       wall_s=args.minutes * 60 - prior["seconds"], log=log_candidate,
+                       confirm_backend=args.confirm_backend)
     if prior.get("best") is not None:
         trk.best = prior["best"]
     trk.candidates = list(prior.get("candidates", []))     # the held-out checks of earlier segments
