@@ -4247,6 +4247,11 @@ int x3_fc_dgrad(const float* G, const void* bits, const void* WcT, long wlo, con
   return rc ? -rc : 1;
 }
 
+// fc weight gradient from the masked gradient Gm (fc_wgrad_gm_x3); nsplit: workgroups a module's user paths are split
+// over.  Contract: with nsplit == 1 the one workgroup of a (module, k tile) STORES its sums (weights and, k tile 0,
+// biases; no atomics, no fixed-point accumulator) instead of adding them, so the result is the gradient only when the
+// module's range of grad holds zeros on entry -- the engine zeroes grad_flat before every backward
+// (runtime/engine.py), and tests/test_x3_partitions.py launches it into zeroed buffers only.  nsplit > 1 adds.
 int x3_fc_wgrad_gm(const void* X, long xlo, int ldx, const void* Gm, long gmlo, float* grad, long w_off, long b_off,
                    int chunk, const int* inv_path, const int* inv_slot, const int* inv_cnt, int layer, int M, int Pmax,
                    int K, int Cout, int P, int E, int T, long br, int nsplit, const float* gamax, hipStream_t st) {
@@ -4271,6 +4276,9 @@ int x3_fc_wgrad_gm(const void* X, long xlo, int ldx, const void* Gm, long gmlo, 
   return rc ? -rc : 1;
 }
 
+// narrow fc weight gradient (fc_wgrad_x3); the path split nsplit = ceil(X3_FCW_TARGET / tiles), 1..Pmax.  Contract: as
+// x3_fc_wgrad_gm -- with nsplit == 1 (one path, or a small X3_FCW_TARGET) the kernel STORES weights and biases
+// instead of adding them, relying on the zeroed grad_flat the engine provides; nsplit > 1 adds.
 int x3_fc_wgrad(const void* X, long xlo, int ldx, const float* G, const void* bits, float* grad, long w_off,
                 long b_off, int chunk, const int* inv_path, const int* inv_slot, const int* inv_cnt, int layer, int M,
                 int Pmax, int K, int Cout, int P, int E, int T, long br, float gs, const float* gamax, hipStream_t st) {

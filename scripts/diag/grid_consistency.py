@@ -1,6 +1,7 @@
 """Backward of every trunk layer at the bench shape under two grid settings (the round-5 whole-round grids vs the
 earlier by-work grids), on the same data in one process: the weight gradients and input gradients must agree to
 the fp32 summation-order level.  A grid partition that drops or repeats work shows up as an O(1) difference.
+The suite's own check of these partitions, against float64 at a small shape: tests/test_x3_partitions.py.
 
     python scripts/diag/grid_consistency.py --paths 64
 """
