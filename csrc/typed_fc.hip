@@ -224,6 +224,32 @@ int launch_typed_fc_fwd(const float* x, int K, const float* flat, long off, long
   return (int)hipGetLastError();
 }
 
+// Dynamic LDS bytes a typed_fc_dgrad_kernel workgroup may ask for: the device's per-workgroup LDS limit for a kernel
+// that has not opted in to more (hipDeviceAttributeMaxSharedMemoryPerBlock) less the kernel's static LDS
+// (hipFuncAttributes.sharedSizeBytes: act[16] + nact_s + nid_s = 72 B), and no more than the runtime reports for this
+// kernel (hipFuncAttributes.maxDynamicSharedSizeBytes).  Read once on the host; -1 where there is no device to ask.
+int typed_fc_dgrad_lds_limit() {
+  static const int limit = [] {
+    hipFuncAttributes a;
+    int dev = 0, per_wg = 0;
+    if (hipFuncGetAttributes(&a, reinterpret_cast<const void*>(typed_fc_dgrad_kernel)) != hipSuccess ||
+        hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&per_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+      (void)hipGetLastError();
+      return -1;
+    }
+    long lim = (long)per_wg - (long)a.sharedSizeBytes;
+    if (a.maxDynamicSharedSizeBytes > 0 && (long)a.maxDynamicSharedSizeBytes < lim) lim = a.maxDynamicSharedSizeBytes;
+    return lim > 0 ? (int)lim : -1;
+  }();
+  return limit;
+}
+
+// The largest request is M = 16, C = 64: 65 536 B of dynamic LDS beside the 72 B of static.  The MI355X admits it: its
+// hipDeviceAttributeMaxSharedMemoryPerBlock reads 163 840 B (the CU's whole 160 KiB, no opt-in needed) and the
+// function above returns 163 768, so every shape this launcher accepts fits there.  On a device with a smaller limit
+// a shape whose request does not fit is refused with -1 before anything is launched (ops/typed_fc.py sends such a
+// layer's input gradient to launch_typed_fc_dgrad_mfma, which reads the same relu mask).
 int launch_typed_fc_dgrad(const float* dy, int K, const float* flat, long off, long chunk, int C, int M,
                           const float* mask, const int* types, int P, int rpp, const void* relu, float* dx,
                           hipStream_t stream) {
@@ -231,6 +257,7 @@ int launch_typed_fc_dgrad(const float* dy, int K, const float* flat, long off, l
   if (C > TF_MAXC || M > TF_MAXM || P < 1 || rpp < 1) return -1;
   dim3 grid(P, (rpp + TF_RT - 1) / TF_RT);
   const size_t lds = (size_t)M * TF_RT * C * sizeof(float);
+  if ((long)lds > (long)typed_fc_dgrad_lds_limit()) return -1;
   typed_fc_dgrad_kernel<<<grid, 256, lds, stream>>>(dy, K, flat, off, chunk, C, M, mask, types, rpp,
                                                     (const uint8_t*)relu, dx);
   return (int)hipGetLastError();

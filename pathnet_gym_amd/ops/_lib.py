@@ -114,6 +114,7 @@ _SIGS = {
     "launch_ga_compact_ex": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P],
     "launch_typed_fc_fwd": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],
     "launch_typed_fc_dgrad": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],
+    "typed_fc_dgrad_lds_limit": [],
     "launch_typed_fc_wgrad": [P, P, c_int, c_long, c_long, c_int, c_int, c_int, P, P, c_int, P, P, P],
     "launch_typed_fc_fwd_mfma": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],
     "launch_typed_fc_dgrad_mfma": [P, c_int, P, c_long, c_long, c_int, c_int, P, P, c_int, c_int, P, P, P],

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 
-_MFMA = "auto"          # "auto": MFMA when a layer is wider than 64 or M > 16; "always"; "never"
+_MFMA = "auto"          # "auto": MFMA when a layer is wider than 64; "always"; "never" (M > 16 raises in _types)
 
 
 def set_mfma(mode: str):
@@ -35,6 +35,13 @@ def set_mfma(mode: str):
 
 def _use_mfma(C: int) -> bool:
     return _MFMA == "always" or (_MFMA == "auto" and C > 64)
+
+
+def _dgrad_use_mfma(C: int, M: int, mfma: bool) -> bool:
+    """The VALU input-gradient kernel stages M * 16 * C floats in dynamic LDS; a layer whose request is over the
+    device's limit (``typed_fc_dgrad_lds_limit``) takes the MFMA kernel for that launch, whatever ran its forward:
+    both read the same ReLU mask."""
+    return mfma or M * 16 * C * 4 > _lib.lib().typed_fc_dgrad_lds_limit()
 
 
 def _types(store) -> List[torch.Tensor]:
@@ -97,7 +104,8 @@ class _TypedLayer(torch.autograd.Function):
         dx = None
         if ctx.need_dx:
             dx = torch.empty(P * rpp, K, dtype=torch.float32, device=g.device)
-            _lib.call("launch_typed_fc_dgrad_mfma" if mfma else "launch_typed_fc_dgrad", g.data_ptr(), K,
+            dmfma = _dgrad_use_mfma(C, cfg.M, mfma)
+            _lib.call("launch_typed_fc_dgrad_mfma" if dmfma else "launch_typed_fc_dgrad", g.data_ptr(), K,
                       flat.data_ptr(), li["offset"], li["chunk"], C, cfg.M, mask_l.data_ptr(), types.data_ptr(), P,
                       rpp, relu.data_ptr(), dx.data_ptr(), s)
         return gflat, dx, None, None, None, None, None
