@@ -956,6 +956,338 @@ struct DoomCorridor : DoomNav {
   }
 };
 
+// --------------------------------------------------------------------------- the last three Doom levels
+// envs/doom_world_games.py: DoomMyWayHome, DoomPredictPosition, DoomDeathmatch.  The living reward of the first two
+// (-0.0001 a tic) rounds to 0: rewards are integers.
+//
+// DoomMyWayHome is the first world that is not convex: free space is the union of NR rectangular regions (rooms, the
+// dead-end corridor, one doorway per door).  Only the region the player stands in is drawn, and a region is convex,
+// so the painter's order above still holds: door openings (part of the wall's surface), posts, vest.  region_of is the
+// integer rule both implementations share.  The region's constants are picked by selects over the unrolled table.
+// int32 bound of view(): the map spans 416 x 272 world units = 6656 x 4352 sub-units, below the 2^14 of DoomNav::view.
+struct DoomMyWayHome : DoomNav {
+  static constexpr int TIMEOUT = 2100;
+  static constexpr int NR = 10, NROOMS = 5, NSTART = 4, ND = 4, NP = 8;
+  static constexpr int VEST_ROOM = 4, VEST_X = 208, VEST_Z = 208, WALL_T = 16, MARGIN = 16, ROOM_SIZE = 128;
+  static constexpr int SPEED = 4, TURN = 4, TOUCH = 16, DOOR_W = 32, DOOR_H = 70, POST_W = 12, VEST_W = 16, VEST_H = 16;
+  enum { PX, PZ, TH, TIC, WON, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + ND + NP + 1 + 2;
+  struct Region { int x0, z0, x1, z1, doors, marks; };
+  //                                        A  B    C    D  E    F    AB   BC   AD  DE
+  static DEVI Region region(int k) {
+    constexpr int X0[NR] = {0, 144, 288, 0, 144, 336, 128, 272, 48, 128};
+    constexpr int Z0R[NR] = {0, 0, 0, 144, 144, 128, 48, 48, 128, 192};
+    constexpr int X1[NR] = {128, 272, 416, 128, 272, 368, 144, 288, 80, 144};
+    constexpr int Z1R[NR] = {128, 128, 128, 272, 272, 272, 80, 80, 144, 224};
+    constexpr int DOORS[NR] = {3, 10, 9, 6, 8, 4, 10, 10, 5, 10};
+    constexpr int MARKS[NR] = {4, 1, 6, 9, 7, 0, 0, 0, 0, 0};
+    return {X0[k], Z0R[k], X1[k], Z1R[k], DOORS[k], MARKS[k]};
+  }
+  static DEVI int region_of(int px, int pz) {
+    int r = -1;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+      const Region g = region(k);
+      r = (px >= g.x0 * U && px < g.x1 * U && pz >= g.z0 * U && pz < g.z1 * U) ? k : r;
+    }
+    return r;
+  }
+  static DEVI void reset(int* s, const Rng& g) {
+    const int room = g.rand(100, NSTART);
+    int x0 = 0, z0 = 0;
+#pragma unroll
+    for (int k = 0; k < NSTART; ++k) {
+      x0 = room == k ? region(k).x0 : x0;
+      z0 = room == k ? region(k).z0 : z0;
+    }
+    s[PX] = (x0 + MARGIN + g.rand(101, ROOM_SIZE - 2 * MARGIN)) * U;
+    s[PZ] = (z0 + MARGIN + g.rand(102, ROOM_SIZE - 2 * MARGIN)) * U;
+    s[TH] = g.rand(103, 256);
+    s[TIC] = 0;
+    s[WON] = 0;
+  }
+  static DEVI bool over(const int* s) { return s[WON] != 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng&) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = fmodi(s[TH] + TURN * ((a == 2) - (a == 3)), 256);
+    const int fwd = a == 1 ? SPEED * U : 0;
+    const int nx = s[PX] + fdiv(fwd * isin(s[TH]), 256);
+    s[PX] = region_of(nx, s[PZ]) >= 0 ? nx : s[PX];
+    const int nz = s[PZ] + fdiv(fwd * icos(s[TH]), 256);
+    s[PZ] = region_of(s[PX], nz) >= 0 ? nz : s[PZ];
+    const bool touch = iabs(fdiv(s[PX], U) - VEST_X) <= TOUCH && iabs(fdiv(s[PZ], U) - VEST_Z) <= TOUCH;
+    s[WON] = touch;
+    return touch;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+    const int here = max(region_of(s[PX], s[PZ]), 0);
+    Region g = region(0);
+#pragma unroll
+    for (int k = 1; k < NR; ++k) {
+      const Region q = region(k);
+      const bool in = here == k;
+      g = {in ? q.x0 : g.x0, in ? q.z0 : g.z0, in ? q.x1 : g.x1, in ? q.z1 : g.z1, in ? q.doors : g.doors,
+           in ? q.marks : g.marks};
+    }
+    const int xm = fdiv(g.x0 + g.x1, 2), zm = fdiv(g.z0 + g.z1, 2);
+    const int xq = g.x0 + fdiv(g.x1 - g.x0, 4), zq = g.z0 + fdiv(g.z1 - g.z0, 4);
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {               // north (z1), east (x1), south (z0), west (x0)
+      const int x = j == 1 ? g.x1 : j == 3 ? g.x0 : xm, z = j == 0 ? g.z1 : j == 2 ? g.z0 : zm;
+      nav_object(r, NBACK + j, view(x * U - s[PX], z * U - s[PZ], sn, cs, U), DOOR_W, DOOR_H, (g.doors >> j) & 1);
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {               // the corners, then the marker posts of walls n, e, s, w
+      const int x = j < 4 ? ((j == 1 || j == 2) ? g.x1 : g.x0) : (j == 5 ? g.x1 : j == 7 ? g.x0 : xq);
+      const int z = j < 4 ? (j >= 2 ? g.z1 : g.z0) : (j == 4 ? g.z1 : j == 6 ? g.z0 : zq);
+      nav_object(r, NBACK + ND + j, view(x * U - s[PX], z * U - s[PZ], sn, cs, U), POST_W, 2 * FH,
+                 j < 4 || ((g.marks >> (j - 4)) & 1));
+    }
+    nav_object(r, NBACK + ND + NP, view(VEST_X * U - s[PX], VEST_Z * U - s[PZ], sn, cs, U), VEST_W, VEST_H,
+               here == VEST_ROOM);
+    hud(r, NBACK + ND + NP + 1, 100, 0, false);
+  }
+};
+
+struct DoomPredictPosition : DoomNav {
+  static constexpr int TIMEOUT = 700;
+  static constexpr int NP = 5, TURN = 1, TH_MAX = 40, MZ = 120, WALLZ = 128, XMAX = 96, MSPEED = 2, DIRT = 32;
+  static constexpr int LOAD = 48, RSPEED = 8, HIT_W = 12, MON_W = 24, MON_H = 40, POST_W = 12, POST_GAP = 48;
+  static constexpr int RK_W = 8, RK_H = 8, RK_LIFT = 25;
+  enum { TH, TIC, MX, MDIR, RX, RZ, RTH, RACT, AMMOF, KILLED, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + NP + 1 + 1 + 4;
+  static DEVI void reset(int* s, const Rng& g) {
+    s[TH] = 0;
+    s[TIC] = 0;
+    s[RX] = 0;
+    s[RZ] = 0;
+    s[RTH] = 0;
+    s[AMMOF] = 1;
+    s[MX] = g.rand(111, 2 * XMAX + 1) - XMAX;
+    s[MDIR] = g.rand(112, 2) * 2 - 1;
+    s[RACT] = 0;
+    s[KILLED] = 0;
+  }
+  static DEVI bool over(const int* s) {
+    return s[KILLED] != 0 || (s[AMMOF] <= 0 && s[RACT] == 0) || s[TIC] >= TIMEOUT;
+  }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = clampi(s[TH] + TURN * ((a == 2) - (a == 3)), -TH_MAX, TH_MAX);
+    int mdir = (fmodi(s[TIC], DIRT) == 0 && g.rand(110, 2) == 1) ? -s[MDIR] : s[MDIR];
+    const int nmx = s[MX] + mdir * MSPEED;
+    s[MDIR] = iabs(nmx) > XMAX ? -mdir : mdir;
+    s[MX] = clampi(nmx, -XMAX, XMAX);
+    const bool fire = a == 1 && s[TIC] > LOAD && s[AMMOF] > 0;
+    s[AMMOF] -= fire;
+    s[RX] = fire ? 0 : s[RX];
+    s[RZ] = fire ? 0 : s[RZ];
+    s[RTH] = fire ? s[TH] : s[RTH];
+    const bool fly = fire || s[RACT] != 0;
+    s[RX] += fly ? fdiv(RSPEED * U * isin(s[RTH]), 256) : 0;
+    s[RZ] += fly ? fdiv(RSPEED * U * icos(s[RTH]), 256) : 0;
+    const bool arrive = fly && fdiv(s[RZ], U) >= MZ;
+    const bool hit = arrive && iabs(fdiv(s[RX], U) - s[MX]) <= HIT_W;
+    s[RACT] = fly && !arrive;
+    s[KILLED] = hit;
+    return hit;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      nav_object(r, NBACK + k, view((k - NP / 2) * POST_GAP * U, WALLZ * U, sn, cs, U), POST_W, 2 * FH, true);
+    nav_object(r, NBACK + NP, view(s[MX] * U, MZ * U, sn, cs, U), MON_W, MON_H, s[KILLED] == 0);
+    nav_object(r, NBACK + NP + 1, view(s[RX], s[RZ], sn, cs, U), RK_W, RK_H, s[RACT] != 0, RK_LIFT);
+    hud(r, NBACK + NP + 2, 100, s[AMMOF], true);
+  }
+};
+
+struct DoomDeathmatch : DoomNav {
+  static constexpr int TIMEOUT = 6300;
+  static constexpr int NM = 4, NF = 2, NK = 3, NP = 8, ROOM = 96, KROOM = 88, SPEED = 4, TURN = 4, MSPEED = 1;
+  static constexpr int HP = 3, MELEE = 10, STANDOFF = 48, FRANGE = 120, RESPAWN = 32;
+  static constexpr int BITE = 8, DAMAGE = 6, FIRE = 32, FPHASE = 16, FT = 24, FDAMAGE = 10, HIT = 12;
+  static constexpr int HEALTH = 100, HMAX = 100, HEAL = 25, AMMO = 20, AMMO_MAX = 50, AMMO_BOX = 10;
+  static constexpr int PISTOL_DMG = 1, PISTOL_COST = 1, PISTOL_CD = 8, SHOTGUN_DMG = 3, SHOTGUN_COST = 2, SHOTGUN_CD = 16;
+  static constexpr int SWITCH = 8, PSPAWN = 64, PPHASE = 16, PICK = 12, KMULX = 37, KMULZ = 59, SMUL = 41;
+  static constexpr int MON_W = 24, MON_H = 40, SH_W = 20, SH_H = 48, POST_W = 12;
+  static constexpr int KIT_W = 12, KIT_H = 12, BOX_W = 8, BOX_H = 16, SG_W = 24, SG_H = 8;
+  static constexpr int FB_W = 12, FB_H = 12, FB_LIFT = 25, GUN_W = 12, GUN2_W = 20;
+  enum { PX, PZ, TH, HEALTHF, AMMOF, COOL, SWT, WEAPON, HAS2, TIC, MX, MZ = MX + NM, MHP = MZ + NM, MT = MHP + NM,
+         FX = MT + NM, FZ = FX + NF, FVX = FZ + NF, FVZ = FVX + NF, FTF = FVZ + NF, KX = FTF + NF, KZ = KX + NK,
+         ALIVE = KZ + NK, FACT, KACT, COUNTER, STEPS, EPRET, NS };
+  static constexpr int R = NBACK + NP + NK + NM + NF + 4;
+  static constexpr int SPAN = 2 * KROOM + 1, WSPAN = 2 * ROOM + 1;
+  static DEVI int post_x(int k) { return (k == 0 || k >= 6) ? -ROOM : (k == 1 || k == 5) ? 0 : ROOM; }
+  static DEVI int post_z(int k) { return k <= 2 ? -ROOM : (k == 3 || k == 7) ? 0 : ROOM; }
+  // slot k comes in on wall k % 4: north, east, south, west
+  static DEVI void spawn(int* s, int k, const Rng& g, int tic) {
+    const int c = fmodi(g.rand(120 + k, WSPAN) + tic * SMUL, WSPAN) - ROOM;
+    const int w = k & 3;
+    s[MX + k] = w == 1 ? ROOM : w == 3 ? -ROOM : c;
+    s[MZ + k] = w == 0 ? ROOM : w == 2 ? -ROOM : c;
+  }
+  static DEVI V monster(const int* s, int k, int sn, int cs) {
+    return view(s[MX + k] * U - s[PX], s[MZ + k] * U - s[PZ], sn, cs, U);
+  }
+  static DEVI void reset(int* s, const Rng& g) {
+    s[PX] = 0;
+    s[PZ] = 0;
+    s[TH] = g.rand(140, 256);
+    s[HEALTHF] = HEALTH;
+    s[AMMOF] = AMMO;
+    s[COOL] = 0;
+    s[SWT] = 0;
+    s[WEAPON] = 0;
+    s[HAS2] = 0;
+    s[TIC] = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      spawn(s, k, g, 0);
+      s[MHP + k] = HP;
+      s[MT + k] = 0;
+    }
+#pragma unroll
+    for (int j = 0; j < NF; ++j) s[FX + j] = s[FZ + j] = s[FVX + j] = s[FVZ + j] = s[FTF + j] = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) s[KX + k] = s[KZ + k] = 0;
+    s[ALIVE] = (1 << NM) - 1;
+    s[FACT] = 0;
+    s[KACT] = 0;
+  }
+  static DEVI bool over(const int* s) { return s[HEALTHF] <= 0 || s[TIC] >= TIMEOUT; }
+  static DEVI int physics(int* s, int a, const Rng& g) {
+    if (over(s)) return 0;
+    s[TIC] += 1;
+    s[TH] = fmodi(s[TH] + TURN * ((a == 5) - (a == 6)), 256);
+    const int fwd = a == 4, side = (a == 2) - (a == 3);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+    s[PX] = clampi(s[PX] + fdiv(SPEED * U * (fwd * sn + side * cs), 256), -ROOM * U, ROOM * U);
+    s[PZ] = clampi(s[PZ] + fdiv(SPEED * U * (fwd * cs - side * sn), 256), -ROOM * U, ROOM * U);
+    const int wx = fdiv(s[PX], U), wz = fdiv(s[PZ], U);
+    // weapons
+    const int swt = max(s[SWT] - 1, 0);
+    const bool change = a == 7 && swt == 0 && s[HAS2] != 0;
+    s[SWT] = change ? SWITCH : swt;
+    s[WEAPON] = change ? 1 - s[WEAPON] : s[WEAPON];
+    const bool shotgun = s[WEAPON] == 1;
+    const int cost = shotgun ? SHOTGUN_COST : PISTOL_COST;
+    const int cool = max(s[COOL] - 1, 0);
+    const bool fire = a == 1 && cool == 0 && s[SWT] == 0 && s[AMMOF] >= cost;
+    s[COOL] = fire ? (shotgun ? SHOTGUN_CD : PISTOL_CD) : cool;
+    s[AMMOF] -= fire ? cost : 0;
+    int alive = s[ALIVE], fact = s[FACT], kact = s[KACT];
+    int key = BIG;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      const V v = monster(s, k, sn, cs);
+      const bool cand = ((alive >> k) & 1) && covers(v, (k & 1) ? SH_W : MON_W);
+      key = min(key, cand ? v.dz * 8 + k : BIG);
+    }
+    const bool hit = fire && key < BIG;
+    int reward = 0, biting = 0;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+      const bool shot = hit && (key & 7) == k;
+      s[MHP + k] -= shot ? (shotgun ? SHOTGUN_DMG : PISTOL_DMG) : 0;
+      const bool dead = shot && s[MHP + k] <= 0;
+      alive &= ~((dead ? 1 : 0) << k);
+      s[MT + k] = dead ? RESPAWN : s[MT + k];
+      reward += dead;
+      // walk towards the player down to the stop distance; the melee ones bite there
+      const bool walk = (alive >> k) & 1;
+      const int ox = wx - s[MX + k], oz = wz - s[MZ + k];
+      const bool far = max(iabs(ox), iabs(oz)) > ((k & 1) ? STANDOFF : MELEE);
+      s[MX + k] += (walk && far) ? MSPEED * ((ox > 0) - (ox < 0)) : 0;
+      s[MZ + k] += (walk && far) ? MSPEED * ((oz > 0) - (oz < 0)) : 0;
+      biting += walk && !far && !(k & 1);
+    }
+    if (fmodi(s[TIC], BITE) == 0) s[HEALTHF] -= biting * DAMAGE;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {               // fireball j belongs to thrower 2 j + 1
+      const int k = 2 * j + 1;
+      const bool fly = (fact >> j) & 1;
+      s[FTF + j] -= fly;
+      s[FX + j] += fly ? s[FVX + j] : 0;
+      s[FZ + j] += fly ? s[FVZ + j] : 0;
+      const bool arrive = fly && s[FTF + j] <= 0;
+      const bool burn = arrive && iabs(fdiv(s[FX + j], U) - wx) <= HIT && iabs(fdiv(s[FZ + j], U) - wz) <= HIT;
+      s[HEALTHF] -= burn ? FDAMAGE : 0;
+      fact &= ~((arrive ? 1 : 0) << j);
+      const bool near = max(iabs(wx - s[MX + k]), iabs(wz - s[MZ + k])) <= FRANGE;
+      const bool launch = ((alive >> k) & 1) && near && !((fact >> j) & 1) && fmodi(s[TIC] + FPHASE * j, FIRE) == 0;
+      s[FX + j] = launch ? s[MX + k] * U : s[FX + j];
+      s[FZ + j] = launch ? s[MZ + k] * U : s[FZ + j];
+      s[FVX + j] = launch ? fdiv(s[PX] - s[MX + k] * U, FT) : s[FVX + j];
+      s[FVZ + j] = launch ? fdiv(s[PZ] - s[MZ + k] * U, FT) : s[FVZ + j];
+      s[FTF + j] = launch ? FT : s[FTF + j];
+      fact |= (launch ? 1 : 0) << j;
+    }
+    // pickups: medkit, ammunition, shotgun
+    bool pick[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      pick[k] = ((kact >> k) & 1) && iabs(s[KX + k] - wx) <= PICK && iabs(s[KZ + k] - wz) <= PICK;
+      kact &= ~((pick[k] ? 1 : 0) << k);
+    }
+    s[HEALTHF] = pick[0] ? min(s[HEALTHF] + HEAL, HMAX) : s[HEALTHF];
+    s[AMMOF] = pick[1] ? min(s[AMMOF] + AMMO_BOX, AMMO_MAX) : s[AMMOF];
+    s[HAS2] = (s[HAS2] != 0 || pick[2]) ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const bool fresh = fmodi(s[TIC], PSPAWN) == PPHASE * k && !((kact >> k) & 1) && (k != 2 || s[HAS2] == 0);
+      s[KX + k] = fresh ? fmodi(g.rand(130 + k, SPAN) + s[TIC] * KMULX, SPAN) - KROOM : s[KX + k];
+      s[KZ + k] = fresh ? fmodi(g.rand(133 + k, SPAN) + s[TIC] * KMULZ, SPAN) - KROOM : s[KZ + k];
+      kact |= (fresh ? 1 : 0) << k;
+    }
+#pragma unroll
+    for (int k = 0; k < NM; ++k)                 // dead slots come back at their wall
+      if (!((alive >> k) & 1)) {
+        s[MT + k] = max(s[MT + k] - 1, 0);
+        if (s[MT + k] == 0) {
+          alive |= 1 << k;
+          spawn(s, k, g, s[TIC]);
+          s[MHP + k] = HP;
+        }
+      }
+    s[ALIVE] = alive;
+    s[FACT] = fact;
+    s[KACT] = kact;
+    return reward;
+  }
+  static DEVI void scene(const int* s, int16_t* r) {
+    backdrop(r);
+    const int sn = isin(s[TH]), cs = icos(s[TH]);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      nav_object(r, NBACK + k, view(post_x(k) * U - s[PX], post_z(k) * U - s[PZ], sn, cs, U), POST_W, 2 * FH, true);
+#pragma unroll
+    for (int k = 0; k < NK; ++k)
+      nav_object(r, NBACK + NP + k, view(s[KX + k] * U - s[PX], s[KZ + k] * U - s[PZ], sn, cs, U),
+                 k == 0 ? KIT_W : k == 1 ? BOX_W : SG_W, k == 0 ? KIT_H : k == 1 ? BOX_H : SG_H, (s[KACT] >> k) & 1);
+#pragma unroll
+    for (int k = 0; k < NM; ++k)
+      nav_object(r, NBACK + NP + NK + k, monster(s, k, sn, cs), (k & 1) ? SH_W : MON_W, (k & 1) ? SH_H : MON_H,
+                 (s[ALIVE] >> k) & 1);
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+      nav_object(r, NBACK + NP + NK + NM + j, view(s[FX + j] - s[PX], s[FZ + j] - s[PZ], sn, cs, U), FB_W, FB_H,
+                 (s[FACT] >> j) & 1, FB_LIFT);
+    const int gw = s[WEAPON] == 1 ? GUN2_W : GUN_W;              // the gun's width shows the weapon in hand
+    const int i = NBACK + NP + NK + NM + NF;
+    rect(r, i, HUD_Y0 - 20, 80 - fdiv(gw, 2), 20, gw);
+    rect(r, i + 1, HUD_Y0, 0, 210 - HUD_Y0, 160);
+    rect(r, i + 2, HUD_Y0 + 4, 8, 6, fdiv(max(s[HEALTHF], 0) * 3, 5));
+    rect(r, i + 3, HUD_Y0 + 14, 8, 6, max(s[AMMOF], 0) * 2);
+  }
+};
+
 // --------------------------------------------------------------------------- driver
 // mode 0: agent step (actions), mode 1: reset_where(mask).  One thread per env.
 template <class G>
@@ -1011,7 +1343,8 @@ static int launch(void* state, const void* actions, const void* mask, int mode, 
 }  // namespace games
 
 // game ids: 0 Breakout, 1 SpaceInvaders, 2 Alien, 3 MsPacman, 4 Centipede, 5 DoomBasic, 6 DoomDefendCenter,
-// 7 DoomTakeCover, 8 DoomDefendLine, 9 DoomHealthGathering, 10 DoomCorridor
+// 7 DoomTakeCover, 8 DoomDefendLine, 9 DoomHealthGathering, 10 DoomCorridor, 12 DoomMyWayHome, 13 DoomPredictPosition,
+// 14 DoomDeathmatch.  11 stays unassigned: the launcher's contract names it as the id that no game answers to.
 extern "C" int game_layout(int game, int* ns, int* nrects) {
   using namespace games;
   switch (game) {
@@ -1026,6 +1359,9 @@ extern "C" int game_layout(int game, int* ns, int* nrects) {
     case 8: *ns = DoomDefendLine::NS; *nrects = DoomDefendLine::R; return 0;
     case 9: *ns = DoomHealthGathering::NS; *nrects = DoomHealthGathering::R; return 0;
     case 10: *ns = DoomCorridor::NS; *nrects = DoomCorridor::R; return 0;
+    case 12: *ns = DoomMyWayHome::NS; *nrects = DoomMyWayHome::R; return 0;
+    case 13: *ns = DoomPredictPosition::NS; *nrects = DoomPredictPosition::R; return 0;
+    case 14: *ns = DoomDeathmatch::NS; *nrects = DoomDeathmatch::R; return 0;
   }
   return -1;
 }
@@ -1046,6 +1382,9 @@ extern "C" int launch_game_step(int game, void* state, const void* actions, cons
     case 8: return launch<DoomDefendLine>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 9: return launch<DoomHealthGathering>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
     case 10: return launch<DoomCorridor>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 12: return launch<DoomMyWayHome>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 13: return launch<DoomPredictPosition>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
+    case 14: return launch<DoomDeathmatch>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
   }
   return -1;
 }

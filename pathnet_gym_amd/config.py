@@ -298,19 +298,29 @@ def preset(name: str) -> TrainConfig:
                            ga=GAConfig(B=3, fitness="mean"),
                            a2c=A2CConfig(max_time_step=DEVICE_TASK_STEPS))
     doom_single = {"doom-basic": "DoomBasic", "doom_basic": "DoomBasic", "doom-corridor": "DoomCorridor",
-                   "doom-defend-line": "DoomDefendLine", "doom-health": "DoomHealthGathering"}
-    if name in ("doom3", "doom6") or name in doom_single:
+                   "doom-defend-line": "DoomDefendLine", "doom-health": "DoomHealthGathering",
+                   "doom-my-way-home": "DoomMyWayHome", "doom-predict": "DoomPredictPosition",
+                   "doom-deathmatch": "DoomDeathmatch"}
+    if name in ("doom3", "doom6", "doom9", "doom-transfer") or name in doom_single:
         # the synthetic first-person Doom scenarios (envs/doom_games.py): the "pong" network, GA fitness and trunk
         # scale of "atari4".  "doom3" has a 4-way head (DoomBasic / DoomDefendCenter have 4 actions, DoomTakeCover
-        # 3); "doom6" is the six scenarios in LEVEL_NAMES order on the 7-way head DoomCorridor needs.
+        # 3); "doom6" is the six scenarios in LEVEL_NAMES order on the 7-way head DoomCorridor needs.  "doom9" is all
+        # nine levels in LEVEL_NAMES order (envs/doom_world_games.py adds the last three) and "doom-transfer" the
+        # reference's own commented Doom experiment, DoomBasic -> DoomDeathmatch with ACTION_SIZEZ = [8, 8]
+        # (constants.py:17-20); the head is 8-way whenever DoomDeathmatch, which plays "constant-7", is a task.
         if name == "doom3":
             tasks = ["DoomBasic", "DoomDefendCenter", "DoomTakeCover"]
         elif name == "doom6":
             tasks = ["DoomBasic", "DoomCorridor", "DoomDefendCenter", "DoomDefendLine", "DoomHealthGathering",
                      "DoomTakeCover"]
+        elif name == "doom9":
+            tasks = ["DoomBasic", "DoomCorridor", "DoomDefendCenter", "DoomDefendLine", "DoomHealthGathering",
+                     "DoomMyWayHome", "DoomPredictPosition", "DoomTakeCover", "DoomDeathmatch"]
+        elif name == "doom-transfer":
+            tasks = ["DoomBasic", "DoomDeathmatch"]
         else:
             tasks = [doom_single[name]]
-        num_actions = 7 if "DoomCorridor" in tasks else 4
+        num_actions = 8 if "DoomDeathmatch" in tasks else 7 if "DoomCorridor" in tasks else 4
         net = PathNetConfig(L=5, M=10, N=4, input_shape=(160, 120, 4),
                             layers=reference_pixel_layers(5, fc=(256, 256)),
                             trunk_scale="none", num_actions=num_actions, num_tasks=len(tasks))

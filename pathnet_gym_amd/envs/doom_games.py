@@ -39,7 +39,8 @@ heading ``th`` of 256 units a turn.  ``isin`` / ``icos`` read the quarter-wave t
 offset ``(rx, rz)`` from the player is seen at ``dx = (rx icos - rz isin) // 256`` and depth
 ``dz = (rx isin + rz icos) // 256`` and drawn with the projection above when ``0 <= dz <= ZVIEW``; farther it is in
 fog.  A shot hits the nearest living enemy whose drawn rectangle covers screen column ``COL``.  RNG streams: 50-57,
-60-67, 70-72 (DoomHealthGathering), 80-85 (DoomDefendLine), 90 (DoomCorridor).
+60-67, 70-72 (DoomHealthGathering), 80-85 (DoomDefendLine), 90 (DoomCorridor); 100-103 (DoomMyWayHome), 110-112
+(DoomPredictPosition), 120-123, 130-135, 140 (DoomDeathmatch): ``envs/doom_world_games.py``.
 
 Painter's order is fixed per rectangle slot: backdrop, posts, vest, enemies or kits, fireballs, HUD.  Posts stand
 on the walls of a convex room, so whatever inside the room overlaps one on screen is nearer.  Objects of one layer
@@ -778,3 +779,5 @@ DOOM_GAMES = {"DoomBasic": DoomBasicVec, "DoomDefendCenter": DoomDefendCenterVec
               "DoomDefendLine": DoomDefendLineVec, "DoomHealthGathering": DoomHealthGatheringVec,
               "DoomCorridor": DoomCorridorVec}
 GAMES.update(DOOM_GAMES)
+
+from . import doom_world_games  # noqa: E402,F401  (adds DoomMyWayHome, DoomPredictPosition, DoomDeathmatch to GAMES)

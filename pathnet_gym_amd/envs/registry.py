@@ -10,7 +10,9 @@ ids (``gym_doom/__init__.py:18-91``).  Three kinds of env live here:
   the presets), and the SYNTHETIC first-person Doom scenarios ``SynthDoomBasic-v0``,
   ``SynthDoomDefendCenter-v0``, ``SynthDoomTakeCover-v0``, ``SynthDoomDefendLine-v0``,
   ``SynthDoomHealthGathering-v0``, ``SynthDoomCorridor-v0`` (aliases ``DoomBasic``, ``DoomDefendCenter``,
-  ``DoomTakeCover``, ``DoomDefendLine``, ``DoomHealthGathering``, ``DoomCorridor``; ``envs/doom_games.py``).  They are not ALE or ViZDoom games and never answer to ALE ids
+  ``DoomTakeCover``, ``DoomDefendLine``, ``DoomHealthGathering``, ``DoomCorridor``; ``envs/doom_games.py``) and
+  ``SynthDoomMyWayHome-v0``, ``SynthDoomPredictPosition-v0``, ``SynthDoomDeathmatch-v0`` (aliases ``DoomMyWayHome``,
+  ``DoomPredictPosition``, ``DoomDeathmatch``; ``envs/doom_world_games.py``).  They are not ALE or ViZDoom games and never answer to ALE ids
   or to the ``gym_doom/*`` ids, which still need the engine (below);
 * real Gym ids (``Pong-v0``, ``PongNoFrameskip-v4``, ``Alien-v0`` ... or any
   other id): resolved through the batched host bridge ``envs/gym_bridge.py``

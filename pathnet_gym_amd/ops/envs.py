@@ -249,7 +249,9 @@ def rects_stack_push(geom: torch.Tensor, colors, bg, obs_in: torch.Tensor, obs_o
 # ------------------------------------------------------------------ synthetic Atari-style games (csrc/games.hip)
 GAME_IDS = {"Breakout": 0, "SpaceInvaders": 1, "Alien": 2, "MsPacman": 3, "Centipede": 4,
             "DoomBasic": 5, "DoomDefendCenter": 6, "DoomTakeCover": 7, "DoomDefendLine": 8,
-            "DoomHealthGathering": 9, "DoomCorridor": 10}
+            "DoomHealthGathering": 9, "DoomCorridor": 10,
+            # 11 stays unassigned (tests/test_doom_nav_hip.py asks the launcher to refuse it)
+            "DoomMyWayHome": 12, "DoomPredictPosition": 13, "DoomDeathmatch": 14}
 
 
 def game_layout(game: str):

@@ -230,11 +230,70 @@ def doom_corridor_expert(env):
     return torch.where(threat.any(1) & (env.ammo > 0), a, go)
 
 
+# the next region on the way to the vest's room (E) from every region of DoomMyWayHome, the dead-end corridor included
+MY_WAY_HOME_NEXT = (8, 6, 7, 9, 4, 2, 0, 1, 3, 4)
+
+
+def doom_my_way_home_expert(env):
+    """Walk the route: in a room head for the middle of the doorway that leads on (walls are slid along), in a
+    doorway for the middle of the room behind it, in the vest's room for the vest."""
+    from pathnet_gym_amd.envs.doom_games import U
+    r = env.region_of(env.px, env.pz).clamp(min=0)
+    nxt = env.const(MY_WAY_HOME_NEXT)[r]
+    tx = torch.where(r == env.VEST_ROOM, env.VEST_X, (env.rx0[nxt] + env.rx1[nxt]) // 2)
+    tz = torch.where(r == env.VEST_ROOM, env.VEST_Z, (env.rz0[nxt] + env.rz1[nxt]) // 2)
+    dx, dz = env.view(tx * U - env.px, tz * U - env.pz)
+    return _steer(dx, dz, torch.clamp(dz // 3, min=6), 1, 2, 3)
+
+
+def doom_predict_position_expert(env):
+    """Lead the shot: from the heading, where the rocket will cross the monster's line and after how many tics; turn
+    until that place is where the monster will then be (its turns at the ends counted), and fire once loaded when
+    no chance turn falls into the flight."""
+    from pathnet_gym_amd.envs.doom_games import U
+    fd = lambda a, b: torch.div(a, b, rounding_mode="floor")      # noqa: E731
+    vx, vz = fd(env.RSPEED * U * env.isin(env.th), 256), fd(env.RSPEED * U * env.icos(env.th), 256)
+    tics = fd(env.MZ * U + vz - 1, vz)
+    cross = fd(tics * vx, U)
+    span = 2 * env.XMAX
+    m = (env.mx + env.mdir * env.MSPEED * tics + env.XMAX) % (2 * span)      # unfold the turns at the ends
+    pred = torch.where(m > span, 2 * span - m, m) - env.XMAX
+    err = cross - pred
+    quiet = fd(env.tic + tics, env.DIRT) == fd(env.tic, env.DIRT)
+    a = torch.where(err > 0, 3, 2)                                             # TURN_LEFT / TURN_RIGHT
+    a = torch.where(err.abs() <= env.HIT_W // 2, torch.zeros_like(a), a)
+    shoot = (err.abs() <= env.HIT_W // 2) & quiet & (env.tic >= env.LOAD) & (env.ammo > 0)
+    return torch.where(shoot, torch.ones_like(a), a)
+
+
+def doom_deathmatch_expert(env):
+    """Take the shotgun into the hand once owned; shoot whatever is in the sights; fetch the pickup that is of use
+    (the shotgun, a medkit when hurt, ammunition when short); otherwise turn to the nearest living monster."""
+    from pathnet_gym_amd.envs.doom_games import U
+    rx, rz = env.kx * U - env.px[:, None], env.kz * U - env.pz[:, None]
+    useful = torch.stack([env.health <= env.HMAX - env.HEAL, env.ammo <= env.AMMO_MAX - env.AMMO_BOX, ~env.has2], 1)
+    want = env.kact & useful
+    dist = torch.where(want, rx.abs() + rz.abs(), torch.full_like(rx, 1 << 30))
+    k = dist.argmin(1, keepdim=True)
+    dx, dz = env.view(rx, rz)
+    dx, dz = dx.gather(1, k).squeeze(1), dz.gather(1, k).squeeze(1)
+    fetch = _steer(dx, dz, torch.clamp(dz // 4, min=env.PICK - 4), 4, 5, 6)
+    mdx, mdz = env.monsters_view()
+    md = torch.where(env.alive, mdx.abs() + mdz.abs(), torch.full_like(mdx, 1 << 30))
+    tdx = mdx.gather(1, md.argmin(1, keepdim=True)).squeeze(1)
+    a = torch.where(tdx >= 0, 5, 6)                                            # TURN_RIGHT / TURN_LEFT
+    a = torch.where(want.any(1), fetch, a)
+    a = torch.where((env.aim() < env.BIG) & (env.ammo >= env.cost()) & (env.swt == 0), torch.ones_like(a), a)
+    return torch.where(env.has2 & (env.weapon == 0) & (env.swt == 0), torch.full_like(a, 7), a)
+
+
 EXPERTS = {"Pong": pong_expert, "Breakout": breakout_expert, "SpaceInvaders": invaders_expert,
            "Alien": alien_expert, "MsPacman": alien_expert, "Centipede": centipede_expert,
            "DoomBasic": doom_basic_expert, "DoomDefendCenter": doom_defend_center_expert,
            "DoomTakeCover": doom_take_cover_expert, "DoomDefendLine": doom_defend_line_expert,
-           "DoomHealthGathering": doom_health_gathering_expert, "DoomCorridor": doom_corridor_expert}
+           "DoomHealthGathering": doom_health_gathering_expert, "DoomCorridor": doom_corridor_expert,
+           "DoomMyWayHome": doom_my_way_home_expert, "DoomPredictPosition": doom_predict_position_expert,
+           "DoomDeathmatch": doom_deathmatch_expert}
 
 
 def play(game: str, policy: str, n: int, episodes: int, max_steps: int, device, seed: int = 7):
@@ -272,7 +331,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--games", default="Pong,Breakout,SpaceInvaders,Alien,MsPacman,Centipede,"
                                        "DoomBasic,DoomDefendCenter,DoomTakeCover,"
-                                       "DoomDefendLine,DoomHealthGathering,DoomCorridor")
+                                       "DoomDefendLine,DoomHealthGathering,DoomCorridor,"
+                                       "DoomMyWayHome,DoomPredictPosition,DoomDeathmatch")
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--max-steps", type=int, default=27000)

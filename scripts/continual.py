@@ -127,7 +127,8 @@ def main():
     ap.add_argument("--preset", default="atari4",
                     help="atari4 (FF 5-layer trunk) | reference (L=4 + LSTM 256, T=20: the reference's own network) | "
                          "doom3 (FF trunk, 4-way head; --tasks DoomBasic,DoomDefendCenter,DoomTakeCover) | "
-                         "doom6 (7-way head; the six synthetic Doom scenarios)")
+                         "doom6 (7-way head; the six synthetic Doom scenarios) | "
+                         "doom9 (8-way head; all nine levels) | doom-transfer (8-way head; DoomBasic -> DoomDeathmatch)")
     ap.add_argument("--paths", type=int, default=None, help="default: 16 (atari4), the preset's (reference)")
     ap.add_argument("--envs", type=int, default=None, help="default: 16 (atari4), the preset's (reference)")
     ap.add_argument("--tmax", type=int, default=None, help="default: 5 (atari4), the preset's (reference)")
