@@ -1340,6 +1340,183 @@ static int launch(void* state, const void* actions, const void* mask, int mode, 
   return (int)hipGetLastError();
 }
 
+
+// --------------------------------------------------------------------------- meta-Doom
+// The nine Doom levels in one batch (envs/doom_meta_games.py is the torch oracle and states the rule).  State row:
+// [level state, NSU words | level, unlocked, req, total5, hist[9][5] | counter, steps, epret].  The level state is the
+// level's own row without its last three words; words past it are 0.  One thread per env reads `level`, switches to
+// the body instantiated from that level's game struct and, at an episode end, scores the episode into the ledger,
+// picks the next level and builds its state in a second switch.  Scenes are META_RU rectangles per env (slots past
+// the level's R are zeros = hidden); level_out names the level whose scene was written, for the rasteriser's gray
+// table.  `table` is int32 [9][4]: lo, target, n_actions, max_steps per level.
+constexpr int cmaxi(int a, int b) { return a > b ? a : b; }
+template <class G, class... Gs> struct MaxOf {
+  static constexpr int NS = cmaxi(G::NS, MaxOf<Gs...>::NS), R = cmaxi(G::R, MaxOf<Gs...>::R);
+};
+template <class G> struct MaxOf<G> { static constexpr int NS = G::NS, R = G::R; };
+
+struct Meta {
+  static constexpr int NL = 9, NH = 5, PASS5 = 3000, FULL5 = 4950, BONUS5 = 2250, RET_MAX = 1000000;
+  using Max = MaxOf<DoomBasic, DoomCorridor, DoomDefendCenter, DoomDefendLine, DoomHealthGathering, DoomMyWayHome,
+                    DoomPredictPosition, DoomTakeCover, DoomDeathmatch>;
+  static constexpr int NSU = Max::NS, RU = Max::R;
+  enum { LEVEL = NSU, UNLOCKED, REQ, TOTAL5, HIST, COUNTER = HIST + NL * NH, STEPS, EPRET, NS };
+  enum { T_LO, T_TARGET, T_NACT, T_MAXSTEPS, T_COLS };
+};
+
+// f(G{}) for the game struct of `level` (0..8, the doom9 order)
+template <class F>
+DEVI void meta_switch(int level, F&& f) {
+  switch (level) {
+    case 0: f(DoomBasic{}); break;
+    case 1: f(DoomCorridor{}); break;
+    case 2: f(DoomDefendCenter{}); break;
+    case 3: f(DoomDefendLine{}); break;
+    case 4: f(DoomHealthGathering{}); break;
+    case 5: f(DoomMyWayHome{}); break;
+    case 6: f(DoomPredictPosition{}); break;
+    case 7: f(DoomTakeCover{}); break;
+    default: f(DoomDeathmatch{}); break;
+  }
+}
+
+template <class G>
+DEVI void meta_load(int* s, const int* row, bool fresh) {
+  static_assert(G::COUNTER == G::NS - 3 && G::STEPS == G::NS - 2 && G::EPRET == G::NS - 1, "trailer words");
+  for (int i = 0; i < G::NS - 3; ++i) s[i] = fresh ? 0 : row[i];
+  s[G::COUNTER] = row[Meta::COUNTER];
+  s[G::STEPS] = row[Meta::STEPS];
+  s[G::EPRET] = row[Meta::EPRET];
+}
+template <class G>
+DEVI void meta_store(const int* s, int* row) {
+  for (int i = 0; i < G::NS - 3; ++i) row[i] = s[i];
+  row[Meta::COUNTER] = s[G::COUNTER];
+  row[Meta::STEPS] = s[G::STEPS];
+  row[Meta::EPRET] = s[G::EPRET];
+}
+template <class G>
+DEVI void meta_scene(const int* s, int16_t* r) {
+  G::scene(s, r);
+  for (int i = G::R * 4; i < Meta::RU * 4; ++i) r[i] = 0;
+}
+
+// The ledger at an episode end (the order of envs/doom_meta_games.py): returns the next level, writes total5.
+DEVI int meta_ledger(int* row, const int* __restrict__ table, int level, int ret, int* total5_out) {
+  ret = clampi(ret, -Meta::RET_MAX, Meta::RET_MAX);
+  const long lo = table[level * Meta::T_COLS + Meta::T_LO];
+  const long span = (long)table[level * Meta::T_COLS + Meta::T_TARGET] - lo;
+  const long den = span > 0 ? span : 1;
+  const long num = 990L * ((long)ret - lo);
+  long q = num / den;
+  if (num % den != 0 && num < 0) q -= 1;                                   // floor division, den > 0
+  const int score = (int)(q < 0 ? 0 : (q > 1000 ? 1000 : q));
+  int* h = row + Meta::HIST;
+  for (int k = Meta::NH - 1; k > 0; --k) h[level * Meta::NH + k] = h[level * Meta::NH + k - 1];
+  h[level * Meta::NH] = score;
+  int sums[Meta::NL];
+  int total = 0;
+  bool all = true;
+#pragma unroll
+  for (int l = 0; l < Meta::NL; ++l) {
+    int v = 0;
+#pragma unroll
+    for (int k = 0; k < Meta::NH; ++k) v += h[l * Meta::NH + k];
+    sums[l] = v;
+    total += v;
+    all = all && v >= Meta::FULL5;
+  }
+  int unlocked = row[Meta::UNLOCKED];
+#pragma unroll
+  for (int i = Meta::NL - 2; i >= 0; --i)
+    if (sums[i] >= Meta::PASS5) unlocked |= 1 << (i + 1);
+  total += all ? Meta::BONUS5 : 0;
+  const int req = row[Meta::REQ];
+  int next = 0, best = 0x7FFFFFFF;
+#pragma unroll
+  for (int l = 0; l < Meta::NL; ++l)
+    if (((unlocked >> l) & 1) && sums[l] < best) {
+      best = sums[l];
+      next = l;
+    }
+  if (req >= 0 && req < Meta::NL && ((unlocked >> req) & 1)) {
+    next = req;
+    row[Meta::REQ] = -1;
+  }
+  row[Meta::UNLOCKED] = unlocked;
+  row[Meta::TOTAL5] = total;
+  row[Meta::LEVEL] = next;
+  *total5_out = total;
+  return next;
+}
+
+// mode 0: agent step (actions), mode 1: reset_where(mask).  One thread per env, as game_step_kernel.
+__global__ __launch_bounds__(64) void meta_step_kernel(int* __restrict__ state, const int* __restrict__ table,
+                                                       const int* __restrict__ actions,
+                                                       const uint8_t* __restrict__ mask, int mode, int N, uint32_t seed,
+                                                       uint32_t id_base, int frameskip, int max_steps,
+                                                       float* __restrict__ reward, uint8_t* __restrict__ done,
+                                                       float* __restrict__ epret, int16_t* __restrict__ rects,
+                                                       uint8_t* __restrict__ level_out) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N) return;
+  int* row = state + (long)e * Meta::NS;
+  int16_t* sc = rects + (long)e * Meta::RU * 4;
+  const uint32_t env = id_base + (uint32_t)e;                              // RNG identity: the global env index
+  const int level = clampi(row[Meta::LEVEL], 0, Meta::NL - 1);             // a corrupt word never indexes anything
+  int next = level;
+  bool enter = false;                                                      // build `next`'s state below
+  if (mode == 0) {
+    int a = actions[e];
+    if (a >= table[level * Meta::T_COLS + Meta::T_NACT] || a < 0) a = 0;
+    const int cap = min(table[level * Meta::T_COLS + Meta::T_MAXSTEPS], max_steps);
+    int ret = 0;
+    meta_switch(level, [&](auto G_) {
+      using G = decltype(G_);
+      int s[G::NS];
+      meta_load<G>(s, row, false);
+      Rng g{seed, env, (uint32_t)s[G::COUNTER]};
+      int rw = 0;
+      for (int f = 0; f < frameskip; ++f) rw += G::physics(s, a, g);
+      s[G::COUNTER] += 1;
+      s[G::STEPS] += 1;
+      s[G::EPRET] += rw;
+      enter = G::over(s) || s[G::STEPS] >= cap;
+      ret = s[G::EPRET];
+      reward[e] = (float)rw;
+      meta_store<G>(s, row);
+      if (!enter) meta_scene<G>(s, sc);
+    });
+    done[e] = enter;
+    float total = 0.f;
+    if (enter) {
+      int total5;
+      next = meta_ledger(row, table, level, ret, &total5);
+      total = (float)total5 * 0.2f;
+    }
+    epret[e] = total;
+  } else {
+    enter = mask[e] != 0;
+  }
+  if (enter || mode != 0)
+    meta_switch(next, [&](auto G_) {
+      using G = decltype(G_);
+      int s[G::NS];
+      meta_load<G>(s, row, next != level);
+      if (enter) {
+        const Rng g{seed, env, (uint32_t)s[G::COUNTER]};
+        G::reset(s, g);
+        s[G::STEPS] = 0;
+        s[G::EPRET] = 0;
+        s[G::COUNTER] += 1;
+        meta_store<G>(s, row);
+        for (int i = G::NS - 3; i < Meta::NSU; ++i) row[i] = 0;
+      }
+      meta_scene<G>(s, sc);
+    });
+  level_out[e] = (uint8_t)next;
+}
+
 }  // namespace games
 
 // game ids: 0 Breakout, 1 SpaceInvaders, 2 Alien, 3 MsPacman, 4 Centipede, 5 DoomBasic, 6 DoomDefendCenter,
@@ -1387,4 +1564,26 @@ extern "C" int launch_game_step(int game, void* state, const void* actions, cons
     case 14: return launch<DoomDeathmatch>(state, actions, mask, mode, n_actions, N, seed, id_base, frameskip, max_steps, reward, done, epret, rects, st);
   }
   return -1;
+}
+
+// The meta game of the nine Doom levels has entry points of its own (game ids 11 and 15 stay refused above).
+extern "C" int meta_layout(int* ns, int* nrects, int* nlevels) {
+  if (!ns || !nrects || !nlevels) return -22;
+  *ns = games::Meta::NS;
+  *nrects = games::Meta::RU;
+  *nlevels = games::Meta::NL;
+  return 0;
+}
+
+extern "C" int launch_meta_step(void* state, const void* table, const void* actions, const void* mask, int mode, int N,
+                                uint32_t seed, uint32_t id_base, int frameskip, int max_steps, void* reward, void* done,
+                                void* epret, void* rects, void* level_out, hipStream_t st) {
+  if (N <= 0 || !state || !table || !rects || !level_out || (mode != 0 && mode != 1)) return -22;
+  if (mode == 0 && (!actions || !reward || !done || !epret)) return -22;
+  if (mode == 1 && !mask) return -22;
+  games::meta_step_kernel<<<(N + 63) / 64, 64, 0, st>>>((int*)state, (const int*)table, (const int*)actions,
+                                                        (const uint8_t*)mask, mode, N, seed, id_base, frameskip,
+                                                        max_steps, (float*)reward, (uint8_t*)done, (float*)epret,
+                                                        (int16_t*)rects, (uint8_t*)level_out);
+  return (int)hipGetLastError();
 }

@@ -100,9 +100,12 @@ constexpr int RECT_BAND = 8;
 constexpr int RECT_NBAND = (pre::SH + RECT_BAND - 1) / RECT_BAND;
 constexpr int RECT_MW = RECT_MAX / 32;
 
-template <bool RING, bool BANDED = true>
+// LV: rect_gray is [NL][R], one gray table per level, and env stages row min(level[env], NL - 1) of it (the meta game
+// of the nine Doom levels, csrc/games.hip meta_step_kernel, whose envs sit on different levels).
+template <bool RING, bool BANDED = true, bool LV = false>
 __global__ __launch_bounds__(256) void rects_push_kernel(const int16_t* __restrict__ rects,
-                                                         const uint8_t* __restrict__ rect_gray, int R, int bg,
+                                                         const uint8_t* __restrict__ rect_gray,
+                                                         const uint8_t* __restrict__ level, int NL, int R, int bg,
                                                          const uint32_t* __restrict__ obs_in,
                                                          uint32_t* __restrict__ obs_out,
                                                          const uint8_t* __restrict__ reset,
@@ -124,13 +127,15 @@ __global__ __launch_bounds__(256) void rects_push_kernel(const int16_t* __restri
     __syncthreads();
   }
   const int16_t* rr = rects + (long)env * R * 4;
+  const uint8_t* gt = rect_gray;
+  if constexpr (LV) gt += (long)min((int)level[env], NL - 1) * R;
   for (int r = threadIdx.x; r < R; r += 256) {
     int y0 = rr[r * 4 + 0], x0 = rr[r * 4 + 1];
     int y1 = y0 + rr[r * 4 + 2], x1 = x0 + rr[r * 4 + 3];
     y0 = max(y0, 0); x0 = max(x0, 0); y1 = min(y1, SH); x1 = min(x1, SW);
     if (y1 <= y0 || x1 <= x0) y1 = y0 = 0;
     rs_[r] = make_uint2((uint32_t)y0 | ((uint32_t)y1 << 16), (uint32_t)x0 | ((uint32_t)x1 << 16));
-    rg_[r] = rect_gray[r];
+    rg_[r] = gt[r];
     if constexpr (BANDED) {
       if (y1 > y0)
         for (int b = y0 / RECT_BAND; b <= (y1 - 1) / RECT_BAND; ++b) atomicOr(&bmask[b * RECT_MW + (r >> 5)], 1u << (r & 31));
@@ -228,11 +233,11 @@ extern "C" int launch_rects_stack_push(const void* rects, const void* rect_gray,
                                        hipStream_t stream) {
   if (R < 0 || R > RECT_MAX || N <= 0) return -22;
   if (rects_banded(R))
-    rects_push_kernel<false, true><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, R, bg,
+    rects_push_kernel<false, true><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, nullptr, 0, R, bg,
                                                           (const uint32_t*)obs_in, (uint32_t*)obs_out,
                                                           (const uint8_t*)reset, tables, nullptr, 0, nullptr, nullptr);
   else
-    rects_push_kernel<false, false><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, R, bg,
+    rects_push_kernel<false, false><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, nullptr, 0, R, bg,
                                                            (const uint32_t*)obs_in, (uint32_t*)obs_out,
                                                            (const uint8_t*)reset, tables, nullptr, 0, nullptr, nullptr);
   return (int)hipGetLastError();
@@ -247,14 +252,50 @@ extern "C" int launch_rects_ring_push(const void* rects, const void* rect_gray, 
       !frames)
     return -22;
   if (rects_banded(R))
-    rects_push_kernel<true, true><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, R, bg,
+    rects_push_kernel<true, true><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, nullptr, 0, R, bg,
                                                          nullptr, nullptr, (const uint8_t*)reset, tables,
                                                          (uint8_t*)frames, frame_stride, (const uint8_t*)fc_in,
                                                          (uint8_t*)fc_out);
   else
-    rects_push_kernel<true, false><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, R, bg,
+    rects_push_kernel<true, false><<<N, 256, 0, stream>>>((const int16_t*)rects, (const uint8_t*)rect_gray, nullptr, 0, R, bg,
                                                           nullptr, nullptr, (const uint8_t*)reset, tables,
                                                           (uint8_t*)frames, frame_stride, (const uint8_t*)fc_in,
                                                           (uint8_t*)fc_out);
   return (int)hipGetLastError();
+}
+
+// Per-env gray tables: rect_gray [NL][R], level uint8 [N].  The same kernels with LV set, chosen by R as above.
+template <bool RING>
+static int rects_push_lv(const void* rects, const void* rect_gray, const void* level, int NL, int R, int bg,
+                         const void* obs_in, void* obs_out, const void* reset, const int* tables, void* frames,
+                         long frame_stride, const void* fc_in, void* fc_out, int N, hipStream_t stream) {
+  if (rects_banded(R))
+    rects_push_kernel<RING, true, true><<<N, 256, 0, stream>>>(
+        (const int16_t*)rects, (const uint8_t*)rect_gray, (const uint8_t*)level, NL, R, bg, (const uint32_t*)obs_in,
+        (uint32_t*)obs_out, (const uint8_t*)reset, tables, (uint8_t*)frames, frame_stride, (const uint8_t*)fc_in,
+        (uint8_t*)fc_out);
+  else
+    rects_push_kernel<RING, false, true><<<N, 256, 0, stream>>>(
+        (const int16_t*)rects, (const uint8_t*)rect_gray, (const uint8_t*)level, NL, R, bg, (const uint32_t*)obs_in,
+        (uint32_t*)obs_out, (const uint8_t*)reset, tables, (uint8_t*)frames, frame_stride, (const uint8_t*)fc_in,
+        (uint8_t*)fc_out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int launch_rects_stack_push_lv(const void* rects, const void* rect_gray, const void* level, int NL, int R,
+                                          int bg, const void* obs_in, void* obs_out, const void* reset,
+                                          const int* tables, int N, hipStream_t stream) {
+  if (R < 0 || R > RECT_MAX || N <= 0 || NL <= 0 || !level) return -22;
+  return rects_push_lv<false>(rects, rect_gray, level, NL, R, bg, obs_in, obs_out, reset, tables, nullptr, 0, nullptr,
+                              nullptr, N, stream);
+}
+
+extern "C" int launch_rects_ring_push_lv(const void* rects, const void* rect_gray, const void* level, int NL, int R,
+                                         int bg, void* frames, long frame_stride, const void* fc_in, void* fc_out,
+                                         const void* reset, const int* tables, int N, hipStream_t stream) {
+  if (R < 0 || R > RECT_MAX || N <= 0 || NL <= 0 || !level || frame_stride < 160 * 120 || frame_stride % 4 ||
+      !fc_in || !fc_out || !frames)
+    return -22;
+  return rects_push_lv<true>(rects, rect_gray, level, NL, R, bg, nullptr, nullptr, reset, tables, frames, frame_stride,
+                             fc_in, fc_out, N, stream);
 }

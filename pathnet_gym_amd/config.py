@@ -300,7 +300,9 @@ def preset(name: str) -> TrainConfig:
     doom_single = {"doom-basic": "DoomBasic", "doom_basic": "DoomBasic", "doom-corridor": "DoomCorridor",
                    "doom-defend-line": "DoomDefendLine", "doom-health": "DoomHealthGathering",
                    "doom-my-way-home": "DoomMyWayHome", "doom-predict": "DoomPredictPosition",
-                   "doom-deathmatch": "DoomDeathmatch"}
+                   "doom-deathmatch": "DoomDeathmatch",
+                   # the nine levels as ONE task (envs/doom_meta_games.py): the "doom9" network, one task column
+                   "doom-meta": "DoomMeta"}
     if name in ("doom3", "doom6", "doom9", "doom-transfer") or name in doom_single:
         # the synthetic first-person Doom scenarios (envs/doom_games.py): the "pong" network, GA fitness and trunk
         # scale of "atari4".  "doom3" has a 4-way head (DoomBasic / DoomDefendCenter have 4 actions, DoomTakeCover
@@ -320,7 +322,7 @@ def preset(name: str) -> TrainConfig:
             tasks = ["DoomBasic", "DoomDeathmatch"]
         else:
             tasks = [doom_single[name]]
-        num_actions = 8 if "DoomDeathmatch" in tasks else 7 if "DoomCorridor" in tasks else 4
+        num_actions = 8 if "DoomDeathmatch" in tasks or "DoomMeta" in tasks else 7 if "DoomCorridor" in tasks else 4
         net = PathNetConfig(L=5, M=10, N=4, input_shape=(160, 120, 4),
                             layers=reference_pixel_layers(5, fc=(256, 256)),
                             trunk_scale="none", num_actions=num_actions, num_tasks=len(tasks))

@@ -220,6 +220,11 @@ class PixelGameVec(VecEnv):
         from ..ops import envs as henv
         henv.rects16_stack_push(self._rects, self._gray_tab, self._bg_gray, obs_in, obs_out, reset_u8, self._tab32)
 
+    def _hip_ring_push(self, frames, slot, fc_in, fc_out, reset_u8):
+        from ..ops import envs as henv
+        henv.rects16_ring_push(self._rects, self._gray_tab, self._bg_gray, frames, slot, fc_in, fc_out, reset_u8,
+                               self._tab32)
+
     def _commit(self):
         for k, p in self._persist.items():
             t = getattr(self, k)
@@ -358,15 +363,13 @@ class PixelGameVec(VecEnv):
         frames[:, slot] with the next stack's first valid channel (csrc/preprocess.hip rects_push_kernel<true>)."""
         if not self.supports_ring:
             raise RuntimeError(f"{self.id}: the frame ring needs the HIP game backend")
-        from ..ops import envs as henv
         a = actions if actions.dtype == torch.int32 and actions.is_contiguous() else \
             actions.to(torch.int32).contiguous()
         direct = (reward.dtype == torch.float32 and done.dtype == torch.uint8 and epret.dtype == torch.float32
                   and reward.is_contiguous() and done.is_contiguous() and epret.is_contiguous())
         rw, dn, ep = (reward, done, epret) if direct else (self._rw, self._dn, self._ep)
         self._hip_run(a, None, rw, dn, ep)
-        henv.rects16_ring_push(self._rects, self._gray_tab, self._bg_gray, frames, slot, fc_in, fc_out,
-                               dn.reshape(-1), self._tab32)
+        self._hip_ring_push(frames, slot, fc_in, fc_out, dn.reshape(-1))
         if not direct:
             reward.copy_(rw.view(reward.shape))
             done.copy_(dn.view(done.shape).to(done.dtype))

@@ -12,7 +12,8 @@ ids (``gym_doom/__init__.py:18-91``).  Three kinds of env live here:
   ``SynthDoomHealthGathering-v0``, ``SynthDoomCorridor-v0`` (aliases ``DoomBasic``, ``DoomDefendCenter``,
   ``DoomTakeCover``, ``DoomDefendLine``, ``DoomHealthGathering``, ``DoomCorridor``; ``envs/doom_games.py``) and
   ``SynthDoomMyWayHome-v0``, ``SynthDoomPredictPosition-v0``, ``SynthDoomDeathmatch-v0`` (aliases ``DoomMyWayHome``,
-  ``DoomPredictPosition``, ``DoomDeathmatch``; ``envs/doom_world_games.py``).  They are not ALE or ViZDoom games and never answer to ALE ids
+  ``DoomPredictPosition``, ``DoomDeathmatch``; ``envs/doom_world_games.py``), and ``SynthDoomMeta-v0`` (alias
+  ``DoomMeta``; ``envs/doom_meta_games.py``), the nine levels as one curriculum task.  They are not ALE or ViZDoom games and never answer to ALE ids
   or to the ``gym_doom/*`` ids, which still need the engine (below);
 * real Gym ids (``Pong-v0``, ``PongNoFrameskip-v4``, ``Alien-v0`` ... or any
   other id): resolved through the batched host bridge ``envs/gym_bridge.py``
@@ -141,6 +142,18 @@ for _g, _thr in synthetic_thresholds().items():
     for _id in ("Synth" + _g + "-v0", _g):
         register(_id, _f, _thr)
         _SYNTH_ALIASES[_id] = _g
+
+
+def _doom_meta(**kw):
+    from .doom_meta_games import DoomMetaVec
+    return DoomMetaVec(**kw)
+
+
+# the nine synthetic Doom levels as one curriculum task (envs/doom_meta_games.py); its goal of 9000 points is fixed by
+# the rule (the reference's meta-Doom-v0 threshold), not calibrated, so it is not in thresholds.json
+for _id in ("SynthDoomMeta-v0", "DoomMeta"):
+    register(_id, _doom_meta, 9000.0)
+    _SYNTH_ALIASES[_id] = "DoomMeta"
 
 
 def _doom(env_id: str):

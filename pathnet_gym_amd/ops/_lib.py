@@ -72,6 +72,11 @@ _SIGS = {
     "launch_rects_ring_push": [P, P, c_int, c_int, P, c_long, P, P, P, P, c_int, P],
     "launch_game_step": [c_int, P, P, P, c_int, c_int, c_int, c_uint, c_uint, c_int, c_int, P, P, P, P, P],
     "game_layout": [c_int, P, P],
+    # the meta game of the nine Doom levels (csrc/games.hip) and the rasteriser with one gray table per level
+    "meta_layout": [P, P, P],
+    "launch_meta_step": [P, P, P, P, c_int, c_int, c_uint, c_uint, c_int, c_int, P, P, P, P, P, P],
+    "launch_rects_stack_push_lv": [P, P, P, c_int, c_int, c_int, P, P, P, P, c_int, P],
+    "launch_rects_ring_push_lv": [P, P, P, c_int, c_int, c_int, P, c_long, P, P, P, P, c_int, P],
     "fast_conv_fwd": [P, c_int, P, P, P, P, c_long, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_float, c_float, P, P, P],
     "launch_refresh_weights_f16": [P, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P],

@@ -318,3 +318,81 @@ def rects16_ring_push(rects: torch.Tensor, gray_tab: torch.Tensor, bg_gray: int,
     _lib.call("launch_rects_ring_push", rects.data_ptr(), gray_tab.data_ptr(), R, int(bg_gray),
               frames[0, slot].data_ptr(), frames.stride(0), fc_in.data_ptr(), fc_out.data_ptr(), _lib.ptr(reset),
               tables32.data_ptr(), N, _lib.stream())
+
+
+# ------------------------------------------------------------------ meta-Doom: nine levels in one batch
+RECT_MAX = 512                  # csrc/preprocess.hip: rectangles per scene the rasteriser stages in LDS
+
+
+def meta_layout():
+    """(ints of state per env, rectangles per scene, levels) of the meta game (csrc/games.hip Meta)."""
+    ns, nr, nl = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("meta_layout", ctypes.byref(ns), ctypes.byref(nr), ctypes.byref(nl))
+    return ns.value, nr.value, nl.value
+
+
+def meta_step(state: torch.Tensor, table: torch.Tensor, actions, mask, seed: int, frameskip: int, max_steps: int,
+              reward: torch.Tensor, done: torch.Tensor, epret: torch.Tensor, rects: torch.Tensor,
+              level_out: torch.Tensor, id_base: int = 0):
+    """``game_step`` for a batch whose envs sit on different Doom levels: ``table`` int32 [levels, 4] holds
+    (lo, target, n_actions, max_steps) per level; also writes ``level_out`` uint8 [N], the level of each scene."""
+    N = state.shape[0]
+    ns, nr, nl = meta_layout()
+    _lib.check(state, torch.int32, (N, ns), name="state")
+    _lib.check(table, torch.int32, (nl, 4), name="table")
+    _lib.check(rects, torch.int16, (N, nr, 4), name="rects")
+    _lib.check(level_out, torch.uint8, (N,), name="level_out")
+    _lib.check(reward, torch.float32, numel=N, name="reward")
+    _lib.check(done, torch.uint8, numel=N, name="done")
+    _lib.check(epret, torch.float32, numel=N, name="epret")
+    if actions is not None:
+        _lib.check(actions, torch.int32, (N,), name="actions")
+    if mask is not None:
+        _lib.check(mask, torch.uint8, (N,), name="mask")
+    _lib.call("launch_meta_step", state.data_ptr(), table.data_ptr(), _lib.ptr(actions), _lib.ptr(mask),
+              0 if mask is None else 1, N, seed & 0xFFFFFFFF, id_base & 0xFFFFFFFF, frameskip, max_steps,
+              reward.data_ptr(), done.data_ptr(), epret.data_ptr(), rects.data_ptr(), level_out.data_ptr(),
+              _lib.stream())
+
+
+def rects16_stack_push_lv(rects: torch.Tensor, gray_tab: torch.Tensor, level: torch.Tensor, bg_gray: int,
+                          obs_in: torch.Tensor, obs_out: torch.Tensor, reset, tables32: torch.Tensor):
+    """``rects16_stack_push`` with one gray table per level: ``gray_tab`` uint8 [NL, R], ``level`` uint8 [N]; env n
+    is painted with row min(level[n], NL - 1)."""
+    N, R = rects.shape[0], rects.shape[1]
+    _lib.check(rects, torch.int16, (N, R, 4), name="rects")
+    _lib.check(gray_tab, torch.uint8, name="gray_tab")
+    if gray_tab.dim() != 2 or gray_tab.shape[0] < 1 or gray_tab.shape[1] != R:
+        raise ValueError(f"gray_tab {tuple(gray_tab.shape)} is not [levels, {R}]")
+    _lib.check(level, torch.uint8, (N,), name="level")
+    _lib.check(obs_out, torch.uint8, numel=N * 160 * 120 * 4, name="obs_out")
+    _lib.check(obs_in, torch.uint8, numel=N * 160 * 120 * 4, name="obs_in")
+    _lib.check(tables32, torch.int32, name="tables")
+    if reset is not None:
+        _lib.check(reset, torch.uint8, numel=N, name="reset")
+    _lib.call("launch_rects_stack_push_lv", rects.data_ptr(), gray_tab.data_ptr(), level.data_ptr(),
+              gray_tab.shape[0], R, int(bg_gray), obs_in.data_ptr(), obs_out.data_ptr(), _lib.ptr(reset),
+              tables32.data_ptr(), N, _lib.stream())
+
+
+def rects16_ring_push_lv(rects: torch.Tensor, gray_tab: torch.Tensor, level: torch.Tensor, bg_gray: int,
+                         frames: torch.Tensor, slot: int, fc_in: torch.Tensor, fc_out: torch.Tensor, reset,
+                         tables32: torch.Tensor):
+    """Frame-ring form of ``rects16_stack_push_lv`` (see ``rects16_ring_push``)."""
+    N, R = rects.shape[0], rects.shape[1]
+    _lib.check(rects, torch.int16, (N, R, 4), name="rects")
+    _lib.check(gray_tab, torch.uint8, name="gray_tab")
+    if gray_tab.dim() != 2 or gray_tab.shape[0] < 1 or gray_tab.shape[1] != R:
+        raise ValueError(f"gray_tab {tuple(gray_tab.shape)} is not [levels, {R}]")
+    _lib.check(level, torch.uint8, (N,), name="level")
+    _lib.check(frames, torch.uint8, name="frames")
+    if frames.dim() != 3 or frames.shape[0] != N or frames.shape[2] != 160 * 120 or not 0 <= slot < frames.shape[1]:
+        raise ValueError(f"frames {tuple(frames.shape)} / slot {slot} do not match [{N}, slots, 19200]")
+    _lib.check(fc_in, torch.uint8, numel=N, name="fc_in")
+    _lib.check(fc_out, torch.uint8, numel=N, name="fc_out")
+    _lib.check(tables32, torch.int32, name="tables")
+    if reset is not None:
+        _lib.check(reset, torch.uint8, numel=N, name="reset")
+    _lib.call("launch_rects_ring_push_lv", rects.data_ptr(), gray_tab.data_ptr(), level.data_ptr(),
+              gray_tab.shape[0], R, int(bg_gray), frames[0, slot].data_ptr(), frames.stride(0), fc_in.data_ptr(),
+              fc_out.data_ptr(), _lib.ptr(reset), tables32.data_ptr(), N, _lib.stream())

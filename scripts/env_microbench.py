@@ -2,8 +2,14 @@
 """Micro-benchmark of the on-device env step kernels: Pong (packed stack push vs frame ring) and the rectangle
 games' frame-ring step (``game_step`` + ``rects16_ring_push``, timed together and each alone).
 
-    python scripts/env_microbench.py [--envs 2048] [--iters 200] [--games Centipede,DoomBasic,...]
+    python scripts/env_microbench.py [--envs 2048] [--iters 200] [--games Centipede,DoomBasic,...] [--meta]
 Prints one JSON line per variant with the mean kernel time (us) measured with HIP events.
+
+``--meta`` adds the meta game of the nine Doom levels (``meta_step`` + ``rects16_ring_push_lv``): every env on one
+level (nine lines), the levels spread evenly env by env (every wave holds all nine) and in nine contiguous blocks (a
+wave holds one or two), each with the single-table rasteriser on the same padded scenes next to the ``_lv`` one.  The
+envs are held on their levels for the timing: only their own level is unlocked and the table's targets are moved out
+of reach, so no episode scores and nothing unlocks.
 """
 from __future__ import annotations
 
@@ -24,6 +30,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--games", default="Centipede,DoomBasic,DoomDefendCenter,DoomTakeCover",
                     help="rectangle games to time on the frame ring (empty: Pong only)")
+    ap.add_argument("--meta", action="store_true", help="also time the meta game of the nine Doom levels")
     args = ap.parse_args()
     from pathnet_gym_amd import _build
     _build.build()
@@ -82,6 +89,35 @@ def main():
         print(json.dumps({"game": name, "envs": B, "rects": g._rects.shape[1], "state_ints": g._st32.shape[1],
                           "ring_step_us": round(us, 2), "game_step_us": round(us_l, 2),
                           "rects16_ring_push_us": round(us_r, 2)}))
+
+    if not args.meta:
+        return
+    from pathnet_gym_amd.envs.doom.constants import LEVEL_NAMES
+    from pathnet_gym_amd.envs.doom_meta_games import NL, DoomMetaVec
+    ar = torch.arange(B, device=dev)
+    settings = [("all on " + n, torch.full((B,), l, device=dev)) for l, n in enumerate(LEVEL_NAMES)]
+    settings += [("spread env by env", ar % NL), ("nine blocks", ar * NL // B)]
+    for label, levels in settings:
+        m = DoomMetaVec(B, device=dev, seed=3, backend="hip")
+        rows, j = m._st32.clone(), m.NSU
+        rows[:, j] = levels.to(torch.int32)
+        rows[:, j + 1] = (1 << levels).to(torch.int32)
+        m.load_packed(rows)
+        m._level_tab[:, 1] = m._level_tab[:, 0] + 10 ** 6
+        m.reset()
+        for _ in range(50):
+            m.step(torch.randint(0, m.num_actions, (B,), generator=gen).to(dev))
+        assert torch.equal(m._lv8.long(), levels), label
+        a = torch.randint(0, m.num_actions, (B,), generator=gen).to(device=dev, dtype=torch.int32)
+        one = m._gray_tab[int(levels[0])].contiguous()
+        us_l = timeit(lambda: m._hip_run(a, None, r, d, e))
+        us_lv = timeit(lambda: m._hip_ring_push(frames, 5, fc[0], fc[1], d))
+        us_1 = timeit(lambda: henv.rects16_ring_push(m._rects, one, m._bg_gray, frames, 5, fc[0], fc[1], d, m._tab32))
+        us = timeit(lambda: m.step_ring_into(a, frames, 5, fc[0], fc[1], r, d, e))
+        print(json.dumps({"game": "DoomMeta", "levels": label, "envs": B, "rects": m._rects.shape[1],
+                          "state_ints": m._st32.shape[1], "ring_step_us": round(us, 2), "meta_step_us": round(us_l, 2),
+                          "rects16_ring_push_lv_us": round(us_lv, 2), "rects16_ring_push_us": round(us_1, 2)}))
+        m.close()
 
 
 if __name__ == "__main__":
