@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ..envs.control import obs_dim_kwargs
 from ..envs.registry import make
 from ..models.acnet import ACPathNet
 from .ga import express
@@ -112,6 +113,7 @@ def evaluate_model(model: ACPathNet, env_id: str, episodes: int = 1, max_steps: 
     P = model.P
     gen = torch.Generator(device=device).manual_seed(seed) if sample else None
     kw = {} if env_id.startswith("CartPole") else dict(frameskip=frameskip, gray=gray)
+    kw.update(obs_dim_kwargs(env_id, model.cfg.input_shape))
     env = make(env_id, num_envs=P, device=device, seed=seed, backend="torch", **kw)
     obs = env.reset()
     state = model.init_state(P)
@@ -189,6 +191,7 @@ def evaluate_path(net_cfg, flat: torch.Tensor, expressed: np.ndarray, env_id: st
     model.task = task
     gen = torch.Generator(device=device).manual_seed(seed)
     kw = {} if env_id.startswith("CartPole") else dict(frameskip=frameskip, gray=gray)
+    kw.update(obs_dim_kwargs(env_id, net_cfg.input_shape))
     # on a GPU the env steps in its HIP kernel (bit-exact to the torch game, tests/test_envs.py / test_games_hip.py):
     # the torch Pong's per-sub-frame ops made a 7 K-step evaluation take 65 s
     env_backend = "hip" if torch.device(device).type == "cuda" else "torch"

@@ -157,6 +157,8 @@ class PathNetTrainer:
         kw = dict(gray=self.cfg.gray)
         if is_synthetic(name):
             kw["frameskip"] = self.cfg.frameskip
+        from ..envs.control import obs_dim_kwargs
+        kw.update(obs_dim_kwargs(name, self.cfg.net.input_shape))     # vector envs: rows as wide as the net's input
         env_backend = "hip" if self.backend == "hip" else "torch"
         env = make(name, num_envs=self.P * self.E, device=self.device, seed=seed, backend=env_backend, **kw)
         env.set_id_base(self.env_base)

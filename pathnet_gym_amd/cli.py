@@ -32,7 +32,8 @@ def build_parser():
         p.add_argument("--preset", default="pong",
                        help="cartpole-cpu | cartpole | pong | atari4 | reference | doom3 | doom6 | doom9 | doom-transfer | "
                             "doom-basic | doom-corridor | doom-defend-line | doom-health | doom-my-way-home | "
-                            "doom-predict | doom-deathmatch | doom-meta")
+                            "doom-predict | doom-deathmatch | doom-meta | acrobot | mountaincar | control3 | "
+                            "control3-cpu")
         # reference flags (doom_pathnet.py:309-361)
         p.add_argument("--ps_hosts_num", type=int, default=None, help="accepted, ignored (no parameter server)")
         p.add_argument("--worker_hosts_num", type=int, default=None, help="population size (paths per rank)")

@@ -271,6 +271,28 @@ def preset(name: str) -> TrainConfig:
                             trunk_scale="none", num_actions=2)
         return TrainConfig(env="CartPole-v1", tasks=["CartPole-v1"], paths=64, envs_per_path=16,
                            net=net, ga=GAConfig(B=2), a2c=A2CConfig(t_max=5, lr=7e-3, lr_anneal="none"))
+    if name in ("acrobot", "mountaincar", "control3", "control3-cpu", "control3_cpu"):
+        # gym's other two discrete classic-control tasks (envs/control.py) and the three-task vector suite
+        # CartPole-v1 -> Acrobot-v1 -> MountainCar-v0.  One input width (8, every env zero-pads its rows to it)
+        # and one 3-way head (CartPole's policy learns not to use the third action, which plays action 0 there
+        # as any action but 1 does).  The single-task presets keep the "cartpole" network and hyper-parameters
+        # (profiles/control/README.md); the suite has 3 layers of M = 8 modules with N = 2, so three frozen paths
+        # (<= 2 modules per layer each) leave free modules in every layer for the last task.
+        if name in ("acrobot", "mountaincar"):
+            tasks = ["Acrobot-v1" if name == "acrobot" else "MountainCar-v0"]
+            net = PathNetConfig(L=2, M=4, N=2, input_shape=(8,),
+                                layers=[LayerSpec("fc", 32), LayerSpec("fc", 32)],
+                                trunk_scale="none", num_actions=3)
+        else:
+            tasks = ["CartPole-v1", "Acrobot-v1", "MountainCar-v0"]
+            net = PathNetConfig(L=3, M=8, N=2, input_shape=(8,),
+                                layers=[LayerSpec("fc", 32), LayerSpec("fc", 32), LayerSpec("fc", 32)],
+                                trunk_scale="none", num_actions=3, num_tasks=3)
+        a2c = A2CConfig(t_max=5, lr=7e-3, lr_anneal="none")
+        if name in ("control3-cpu", "control3_cpu"):
+            return TrainConfig(env=tasks[0], tasks=tasks, paths=4, envs_per_path=8, net=net, ga=GAConfig(B=2),
+                               backend="torch", compute_dtype="fp32", use_graph=False, a2c=a2c)
+        return TrainConfig(env=tasks[0], tasks=tasks, paths=64, envs_per_path=16, net=net, ga=GAConfig(B=2), a2c=a2c)
     if name == "pong":
         # BASELINE config 3 (headline): Pong pixels, L=3 conv + 2 fc x M=10 modules, N=4 (doom_pathnet.py:354).
         # Two choices make it learn (profiles/solve/ablation_r2/README.md):

@@ -9,6 +9,10 @@ Two implementations share this class: a pure torch one (oracle, CPU) and
 the fused HIP kernel ``cartpole_step`` (``csrc/envs.hip``) on GPU.  Initial
 states use the same counter-based hash RNG in both so they agree bit-for-bit
 up to float rounding of the dynamics.
+
+``obs_dim`` (4..8, default 4) is the width of the returned observation rows: columns 4.. are zeros, so a network
+with a wider vector input (the ``control3`` presets, envs/control.py) can play this task among others.  The default
+returns exactly the state.
 """
 from __future__ import annotations
 
@@ -35,10 +39,12 @@ class CartPoleVec(VecEnv):
     reward_threshold = 475.0
     max_episode_steps = 500
 
-    def __init__(self, num_envs: int, device="cpu", seed: int = 0, backend: str = "torch"):
+    def __init__(self, num_envs: int, device="cpu", seed: int = 0, backend: str = "torch", obs_dim: int = 4):
+        from .control import check_obs_dim
+        self.obs_dim = check_obs_dim(self.id, 4, obs_dim)
         self.num_envs = num_envs
         self.num_actions = 2
-        self.obs_shape = (4,)
+        self.obs_shape = (self.obs_dim,)
         self.obs_dtype = torch.float32
         self.device = torch.device(device)
         self.backend = backend
@@ -61,10 +67,17 @@ class CartPoleVec(VecEnv):
         self.counter += mask.long()
         return torch.where(mask[:, None], init, self.state)
 
+    def observe(self) -> torch.Tensor:
+        """The current observation, [B, obs_dim] fp32 (a new tensor): the state, zero padded past column 4."""
+        if self.obs_dim == 4:
+            return self.state.clone()
+        from .control import pad_obs
+        return pad_obs(self.state, self.obs_dim)
+
     def reset(self):
         allm = torch.ones(self.num_envs, dtype=torch.bool, device=self.device)
         self.reset_where(allm)
-        return self.state.clone()
+        return self.observe()
 
     def reset_where(self, mask):
         hip_state = hasattr(self, "_steps32")
@@ -102,4 +115,4 @@ class CartPoleVec(VecEnv):
         self.ep_ret = self.ep_ret + reward
         ep_return = torch.where(done, self.ep_ret, torch.zeros_like(self.ep_ret))
         self.reset_where(done)
-        return self.state.clone(), reward, done, {"episode_return": ep_return}
+        return self.observe(), reward, done, {"episode_return": ep_return}

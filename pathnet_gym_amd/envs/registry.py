@@ -3,7 +3,9 @@
 Reference tasks are gym Atari ids (``constants.py:14``) and the gym_doom
 ids (``gym_doom/__init__.py:18-91``).  Three kinds of env live here:
 
-* on-device envs: ``CartPole-v1`` (the classic-control dynamics, exact) and
+* on-device envs: ``CartPole-v1``, ``Acrobot-v1`` and ``MountainCar-v0`` (the classic-control dynamics, exact;
+  ``envs/cartpole.py``, ``envs/control.py``; all three take ``obs_dim`` <= 8 and zero-pad their observation rows
+  to it, so one vector network plays all of them) and
   the SYNTHETIC Atari-style games ``SynthPong-v0``, ``SynthBreakout-v0``,
   ``SynthSpaceInvaders-v0``, ``SynthAlien-v0``, ``SynthMsPacman-v0``,
   ``SynthCentipede-v0`` (short aliases ``Pong``, ``Breakout``, ... are kept for
@@ -114,6 +116,15 @@ def _cartpole(**kw):
     return CartPoleVec(**kw)
 
 
+def _control(cls_name):
+    def f(**kw):
+        from . import control
+        for k in ("frameskip", "gray", "no_op_max"):
+            kw.pop(k, None)
+        return getattr(control, cls_name)(**kw)
+    return f
+
+
 def _atari_game(name):
     def f(**kw):
         from .atari_games import make_game
@@ -137,6 +148,8 @@ def synthetic_thresholds() -> Dict[str, float]:
 
 
 register("CartPole-v1", _cartpole, 475.0)
+register("Acrobot-v1", _control("AcrobotVec"), -100.0)
+register("MountainCar-v0", _control("MountainCarVec"), -110.0)
 for _g, _thr in synthetic_thresholds().items():
     _f = _pong if _g == "Pong" else _atari_game(_g)
     for _id in ("Synth" + _g + "-v0", _g):

@@ -63,6 +63,11 @@ _SIGS = {
     "launch_pong_step_ring_split": [P, P, P, c_int, P, c_long, P, P, P, P, P, P, c_int, c_uint, c_int, c_int, c_int,
                                     c_int, c_int, c_int, c_int, c_int, c_uint, c_int, c_int, P],
     "launch_cartpole_step": [P, P, P, P, P, c_int, c_uint, c_uint, c_int, P, P, P, P, P, P],
+    # csrc/control.hip: launch_cartpole_step's arguments plus the fp32 row stride obs_ld after obs_f32
+    "launch_acrobot_step": [P, P, P, P, P, c_int, c_uint, c_uint, c_int, P, c_int, P, P, P, P, P],
+    "launch_mountaincar_step": [P, P, P, P, P, c_int, c_uint, c_uint, c_int, P, c_int, P, P, P, P, P],
+    "launch_cartpole_step_padded": [P, P, P, P, P, c_int, c_uint, c_uint, c_int, P, c_int, P, P, P, P, P],
+    "launch_control_observe": [c_int, P, c_int, P, c_int, P, P],
     "launch_pong_digit_tables": [P, c_int, c_int, c_int, c_int, c_int, P],
     "x3_refresh_weights_all": [P, c_int, P, P, P, c_int, c_int, P, P],
     "launch_opt_tail": [P, P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, P, P],

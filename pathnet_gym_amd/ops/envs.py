@@ -1,4 +1,4 @@
-"""HIP env stepping (``csrc/envs.hip``) for the on-device environments.
+"""HIP env stepping (``csrc/envs.hip``, ``csrc/control.hip``) for the on-device environments.
 
 Two entry points per env:
 * ``*_step_into``: engine path -- reads obs slot t, writes slot t+1 and the
@@ -186,6 +186,8 @@ def cartpole_step_into(env, actions, obs_bf16_out, reward, done, epret, obs_f32_
 
 
 def cartpole_step(env, actions):
+    if getattr(env, "obs_dim", 4) != 4:
+        return control_step(env, actions)          # padded rows: csrc/control.hip
     B = env.num_envs
     dev = env.state.device
     obs = torch.empty(B, 4, dtype=torch.float32, device=dev)
@@ -194,6 +196,117 @@ def cartpole_step(env, actions):
     epret = torch.empty(B, dtype=torch.float32, device=dev)
     cartpole_step_into(env, actions.to(torch.int32).contiguous(), None, reward, done, epret, obs_f32_out=obs)
     return obs, reward, done.bool(), {"episode_return": epret}
+
+
+# ------------------------------------------------------------------ Acrobot, MountainCar, padded CartPole
+# csrc/control.hip: one launcher per game, all with the argument list of launch_cartpole_step plus the fp32 row
+# stride obs_ld.  The envs share CartPoleVec's attribute names, so the device state is synced the same way.
+control_sync_to_device = cartpole_sync_to_device
+
+
+def control_launcher(env) -> str:
+    """The csrc/control.hip launcher that steps ``env`` (a missing kernel is an error, never a torch fallback)."""
+    name = getattr(env, "hip_launcher", None)
+    if name is None and getattr(env, "id", "") == "CartPole-v1":
+        name = "launch_cartpole_step_padded"
+    if name not in ("launch_acrobot_step", "launch_mountaincar_step", "launch_cartpole_step_padded"):
+        raise NotImplementedError(f"no HIP step kernel for vector env {getattr(env, 'id', type(env).__name__)!r}")
+    return name
+
+
+def _control_args(env, name, actions, obs_bf16_out, reward, done, epret, obs_f32_out, obs_ld):
+    """Validate one step's buffers for launcher ``name`` and return its argument list."""
+    B = env.num_envs
+    if control_launcher(env) != name:
+        raise TypeError(f"{name}: env {env.id!r} is stepped by {control_launcher(env)}")
+    if not hasattr(env, "_steps32"):
+        control_sync_to_device(env)
+    ld = int(env.obs_dim if obs_ld is None else obs_ld)
+    native = int(getattr(env, "native_obs_dim", 4))
+    if not native <= ld <= 8:
+        raise ValueError(f"{env.id}: obs_ld={ld} outside [{native}, 8]")
+    _lib.check(actions, torch.int32, (B,), name="actions")
+    _lib.check(env.state, torch.float32, (B, int(getattr(env, "state_dim", 4))), name="state")
+    _lib.check(env._steps32, torch.int32, (B,), name="steps")
+    _lib.check(env._ctr32, torch.int32, (B,), name="counter")
+    _lib.check(env.ep_ret, torch.float32, (B,), name="ep_ret")
+    _lib.check(reward, torch.float32, numel=B, name="reward")
+    _lib.check(done, torch.uint8, numel=B, name="done")
+    _lib.check(epret, torch.float32, numel=B, name="epret")
+    if obs_bf16_out is not None:
+        _lib.check(obs_bf16_out, torch.bfloat16, numel=B * 8, name="obs_bf16")
+    if obs_f32_out is not None:
+        _lib.check(obs_f32_out, torch.float32, numel=B * ld, name="obs_f32")
+    return (env.state.data_ptr(), env._steps32.data_ptr(), env.ep_ret.data_ptr(), env._ctr32.data_ptr(),
+            actions.data_ptr(), B, env.seed_int, _id_base(env), env.max_episode_steps, _lib.ptr(obs_f32_out), ld,
+            _lib.ptr(obs_bf16_out), reward.data_ptr(), done.data_ptr(), epret.data_ptr(), _lib.stream())
+
+
+def acrobot_step_into(env, actions, obs_bf16_out, reward, done, epret, obs_f32_out=None, obs_ld=None):
+    """One Acrobot-v1 step of every env.  ``obs_f32_out``: fp32 rows of stride ``obs_ld`` floats (default
+    env.obs_dim), columns past the native width written as zeros; ``obs_bf16_out``: bf16 [B, 8] rows.  Either may be
+    None."""
+    st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s = _control_args(
+        env, "launch_acrobot_step", actions, obs_bf16_out, reward, done, epret, obs_f32_out, obs_ld)
+    _lib.call("launch_acrobot_step", st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s)
+
+
+def mountaincar_step_into(env, actions, obs_bf16_out, reward, done, epret, obs_f32_out=None, obs_ld=None):
+    """One MountainCar-v0 step of every env (buffers as acrobot_step_into)."""
+    st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s = _control_args(
+        env, "launch_mountaincar_step", actions, obs_bf16_out, reward, done, epret, obs_f32_out, obs_ld)
+    _lib.call("launch_mountaincar_step", st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s)
+
+
+def cartpole_padded_step_into(env, actions, obs_bf16_out, reward, done, epret, obs_f32_out=None, obs_ld=None):
+    """One CartPole-v1 step of every env with observation rows of any width 4..8 (buffers as acrobot_step_into)."""
+    st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s = _control_args(
+        env, "launch_cartpole_step_padded", actions, obs_bf16_out, reward, done, epret, obs_f32_out, obs_ld)
+    _lib.call("launch_cartpole_step_padded", st, n, er, c, a, B, seed, base, lim, of, ld, ob, r, d, eo, s)
+
+
+_CONTROL_STEP_INTO = {"launch_acrobot_step": acrobot_step_into, "launch_mountaincar_step": mountaincar_step_into,
+                      "launch_cartpole_step_padded": cartpole_padded_step_into}
+
+
+def control_step_into(env, actions, obs_bf16_out, reward, done, epret, obs_f32_out=None, obs_ld=None):
+    """The step of whichever of the three envs ``env`` is."""
+    _CONTROL_STEP_INTO[control_launcher(env)](env, actions, obs_bf16_out, reward, done, epret, obs_f32_out, obs_ld)
+
+
+_CONTROL_GAME = {"launch_cartpole_step_padded": 0, "launch_acrobot_step": 1, "launch_mountaincar_step": 2}
+
+
+def control_observe(env, obs_ld=None) -> torch.Tensor:
+    """The observation rows of the env's current state, [B, obs_ld (default env.obs_dim)] fp32, computed by the
+    kernel that also writes them after a step: an engine that starts or resumes from a stored state reads exactly
+    what a rollout would have handed it."""
+    B = env.num_envs
+    game = _CONTROL_GAME[control_launcher(env)]
+    ld = int(env.obs_dim if obs_ld is None else obs_ld)
+    native = int(getattr(env, "native_obs_dim", 4))
+    if not native <= ld <= 8:
+        raise ValueError(f"{env.id}: obs_ld={ld} outside [{native}, 8]")
+    state = env.state.float().contiguous()
+    _lib.check(state, torch.float32, (B, int(getattr(env, "state_dim", 4))), name="state")
+    out = torch.empty(B, ld, dtype=torch.float32, device=state.device)
+    _lib.call("launch_control_observe", game, state.data_ptr(), B, out.data_ptr(), ld, None, _lib.stream())
+    return out
+
+
+def control_step(env, actions):
+    B = env.num_envs
+    dev = env.state.device
+    obs = torch.empty(B, env.obs_dim, dtype=torch.float32, device=dev)
+    reward = torch.empty(B, dtype=torch.float32, device=dev)
+    done = torch.empty(B, dtype=torch.uint8, device=dev)
+    epret = torch.empty(B, dtype=torch.float32, device=dev)
+    control_step_into(env, actions.to(torch.int32).contiguous(), None, reward, done, epret, obs_f32_out=obs)
+    return obs, reward, done.bool(), {"episode_return": epret}
+
+
+acrobot_step = mountaincar_step = control_step
+acrobot_sync_to_device = mountaincar_sync_to_device = control_sync_to_device
 
 
 def obs_to_bf16_padded(obs_f32: torch.Tensor) -> torch.Tensor:

@@ -105,6 +105,16 @@ class HipEngine:
             self._obs_bufs = [torch.zeros(T, B, hp.geoms[0].ldx, dtype=torch.float32, device=dev) for _ in range(2)]
         else:
             self._obs_bufs = [torch.zeros(T, B, 8, dtype=torch.bfloat16, device=dev) for _ in range(2)]
+        # vector envs: CartPole-v1 at its own width 4 keeps launch_cartpole_step (csrc/envs.hip); every other vector
+        # env, and CartPole with rows padded to a wider net input, steps in csrc/control.hip
+        self._vector_padded = False
+        if not self.pixels and not hasattr(env, "step_into"):
+            self._vector_padded = not (getattr(env, "id", "") == "CartPole-v1" and getattr(env, "obs_dim", 4) == 4)
+            if self._vector_padded:
+                henv.control_launcher(env)          # an env without a HIP step kernel is refused here, by name
+            if hp.f32 and self._vector_padded and hp.geoms[0].ldx != env.obs_dim:
+                raise ValueError(f"{env.id}: obs_dim={env.obs_dim} does not match the net's input row of "
+                                 f"{hp.geoms[0].ldx} floats")
         self.acts, self.bits, self.bits_rows, self.grads = [], [], [], []
         # conv-layer output gradients kept in bf16 where the specialised dgrad / wgrad kernels take them
         # (grads[0] is 1.5 GB and grads[1] 0.3 GB in fp32 at the bench shape)
@@ -260,9 +270,18 @@ class HipEngine:
         if self.pixels:
             self.set_obs_stack0(o.reshape(self.B, -1))
         elif self.hip.f32:
-            self.obs[0].copy_(env.state.float().reshape(self.B, -1))
+            self.obs[0].copy_(self._vector_obs(env))
         else:
-            self.obs[0].copy_(henv.obs_to_bf16_padded(env.state.float()))
+            self.obs[0].copy_(henv.obs_to_bf16_padded(self._vector_obs(env)))
+
+    def _vector_obs(self, env) -> torch.Tensor:
+        """A vector env's current observation [B, net input width] fp32 (zero padded by the env, envs/control.py)."""
+        o = (env.observe() if hasattr(env, "observe") else env.state).float().reshape(self.B, -1)
+        K = int(self.model.cfg.input_shape[0])
+        if o.shape[1] != K:
+            raise ValueError(f"{env.id}: observation width {o.shape[1]} does not match the net's input_shape "
+                             f"{tuple(self.model.cfg.input_shape)}; build the env with obs_dim={K}")
+        return o
 
     # -- packed-stack views of the observation buffers (tests, checkpoints) -------
     def obs_stack(self, t: int) -> torch.Tensor:
@@ -360,6 +379,14 @@ class HipEngine:
         elif self.pixels:
             henv.pong_step_into(env, self.actions[t], self._obs_at(t), self._obs_at(t + 1), self.rewards[t],
                                 self.dones[t], self.epret[t])
+        elif self._vector_padded:
+            # Acrobot-v1, MountainCar-v0, or CartPole-v1 with padded rows (csrc/control.hip)
+            if self.hip.f32:
+                henv.control_step_into(env, self.actions[t], None, self.rewards[t], self.dones[t], self.epret[t],
+                                       obs_f32_out=self._obs_at(t + 1), obs_ld=self.hip.geoms[0].ldx)
+            else:
+                henv.control_step_into(env, self.actions[t], self._obs_at(t + 1), self.rewards[t], self.dones[t],
+                                       self.epret[t])
         elif self.hip.f32:
             henv.cartpole_step_into(env, self.actions[t], None, self.rewards[t], self.dones[t], self.epret[t],
                                     obs_f32_out=self._obs_at(t + 1))

@@ -14,8 +14,9 @@ first ``quota`` episodes, advances the step clock and counts the envs still shor
 captured once per parity as a hipGraph, so a whole evaluation is graph replays plus one 4-byte read of that count
 every ``check_every`` chunks.
 
-Envelope: the on-device envs (CartPole-v1 and the synthetic games of envs/registry.py), E <= 32, feed-forward nets
-and LSTM nets whose widths the fused cells take (multiples of 64).  ``unsupported_reason`` names what is outside it.
+Envelope: the on-device envs (CartPole-v1, Acrobot-v1, MountainCar-v0 and the synthetic games of envs/registry.py),
+E <= 32, feed-forward nets and LSTM nets whose widths the fused cells take (multiples of 64).  ``unsupported_reason``
+names what is outside it.
 """
 from __future__ import annotations
 
@@ -66,8 +67,13 @@ def unsupported_reason(net_cfg, env_id: str, compute_dtype: Optional[str] = None
     ``backend="auto"`` (algo/evaluate.py) asks this before it picks the hip backend."""
     from ..envs.registry import is_synthetic
     from ..ops.pathnet_ops import geometry_unsupported_reason
-    if not (is_synthetic(env_id) or env_id == "CartPole-v1"):
+    from ..envs.control import CONTROL_IDS, obs_dim_kwargs
+    if not (is_synthetic(env_id) or env_id in CONTROL_IDS):
         return f"env {env_id!r} is stepped on the host (Gym bridge), not by a HIP kernel"
+    try:
+        obs_dim_kwargs(env_id, net_cfg.input_shape)
+    except ValueError as e:
+        return str(e)
     if envs_per_path > MAX_ENVS_PER_PATH:
         return f"envs_per_path={envs_per_path} > {MAX_ENVS_PER_PATH} (replicate the path instead)"
     if envs_per_path % min_envs_per_path(net_cfg) != 0:
@@ -124,6 +130,8 @@ class HipEvaluator:
         self.model = ACPathNet(net_cfg, self.P, self.device, "hip", compute_dtype=self.compute_dtype)
         self.model.store.flat.requires_grad_(False)          # never trained
         kw = {} if env_id.startswith("CartPole") else dict(frameskip=frameskip, gray=gray)
+        from ..envs.control import obs_dim_kwargs
+        kw.update(obs_dim_kwargs(env_id, net_cfg.input_shape))
         self.env = make(env_id, num_envs=self.B, device=self.device, seed=env_seed, backend="hip", **kw)
         self.env.reset()
         if frame_ring is None:
@@ -166,14 +174,15 @@ class HipEvaluator:
     # -- env state: snapshot after the first reset, restored in place before every run -------------------------------
     def _snapshot_env(self):
         from ..envs.cartpole import CartPoleVec
+        from ..envs.control import ControlVec
         from ..envs.pong import PongVec
         from ..ops import envs as henv
         env = self.env
         # the kernels' own state buffers exist before the snapshot (they are otherwise made by the first step)
         if isinstance(env, PongVec) and not hasattr(env, "_st32"):
             henv.pong_sync_to_device(env)
-        if isinstance(env, CartPoleVec) and not hasattr(env, "_steps32"):
-            henv.cartpole_sync_to_device(env)
+        if isinstance(env, (CartPoleVec, ControlVec)) and not hasattr(env, "_steps32"):
+            henv.control_sync_to_device(env)
         self._env_obs0 = env.obs.clone() if self.engine.pixels else None
         self._env_snap = [(k, v, v.clone()) for k, v in vars(env).items()
                           if isinstance(v, torch.Tensor) and v.device.type == "cuda" and k != "obs"]

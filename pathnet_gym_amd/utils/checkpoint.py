@@ -142,6 +142,10 @@ def _restack_current_frame(trainer):
     """Light checkpoints: every env's stack entering the next rollout = its current frame x 4 (episode-start rule)."""
     env = trainer.env
     if not hasattr(env, "frame"):
+        # vector envs (CartPole-v1, Acrobot-v1, MountainCar-v0): the observation is a function of the restored
+        # state, so a light checkpoint resumes exactly
+        if hasattr(env, "observe") and trainer.engine is not None and not trainer.engine.pixels:
+            trainer.engine.load_obs(env)
         return
     _sync_env_from_device(env)
     f = env.frame()                                   # [N, H, W] uint8
@@ -208,7 +212,7 @@ def load(trainer, path: str, strict: bool = True):
             henv.pong_sync_to_device(env)
         if hasattr(env, "_steps32"):
             from ..ops import envs as henv
-            henv.cartpole_sync_to_device(env)
+            henv.control_sync_to_device(env)          # CartPole-v1, Acrobot-v1, MountainCar-v0 alike
         if trainer.engine is not None:
             eng = trainer.engine
             eng.ctr.copy_(r["engine.ctr"].to(dev))
