@@ -153,19 +153,26 @@ def path_rows(x, ly, p, shifted=False):
     return xp[:, :ly.K]
 
 
-def forward_ref(ly, x, W, b, acts, bf16_store, shifted=False):
+def forward_ref(ly, x, W, b, acts, bf16_store, shifted=False, offset=0.0, bias_slack=None):
     """x [T, P, E, in_feat] (raw: uint8 pixels for layer 0), W [M, K, Cout], b [M, Cout] float64, acts[p] = module of
-    every active slot  ->  y, its bound [T, P, E, out_feat], and per path pre / slot bound [cnt, T*E*HWo, Cout]."""
+    every active slot  ->  y, its bound [T, P, E, out_feat], and per path pre / slot bound [cnt, T*E*HWo, Cout].
+    ``offset`` (fp16-offset operands, csrc/conv_fast.hip F16): every operand enters the GEMM as offset + x, so
+    pre = in_scale * ((offset + x) @ W) + b with ``b`` the corrected bias and the bound on (offset + |x|) @ |W|;
+    ``bias_slack`` [M, Cout] is added to the slot bound (the rounding of that corrected bias)."""
     T, P, E, _ = x.shape
     y = torch.zeros(T, P, E, ly.out_feat, dtype=torch.float64)
     yb = torch.zeros_like(y)
     pres, bounds = [], []
     for p in range(P):
         A = path_rows(x, ly, p, shifted)
+        if offset:
+            A = A + offset
         pre = torch.stack([ly.in_scale * (A @ W[j]) + b[j] for j in acts[p]]) if len(acts[p]) else \
             torch.zeros(0, A.shape[0], ly.Cout, dtype=torch.float64)
         bnd = torch.stack([ly.K * EPS * ly.in_scale * (A.abs() @ W[j].abs()) for j in acts[p]]) + EPS * pre.abs() \
             if len(acts[p]) else torch.zeros_like(pre)
+        if bias_slack is not None and len(acts[p]):
+            bnd = bnd + torch.stack([bias_slack[j] for j in acts[p]])[:, None, :]
         yp = ly.out_scale * torch.relu(pre).sum(0)
         ybp = ly.out_scale * bnd.sum(0)
         if bf16_store:
@@ -178,12 +185,17 @@ def forward_ref(ly, x, W, b, acts, bf16_store, shifted=False):
 
 
 def backward_ref(ly, x, G, bits, Wd, acts, M, g_scale, round_w=False, round_d=False, bias_rounded=False,
-                 want_dx=True):
+                 want_dx=True, scale_after=False):
     """Gradients of one layer from G [T, P, E, out_feat] and the ReLU bits[p] [cnt, R, Cout] (bool): dW [M, K, Cout],
     db [M, Cout], dX [T, P, E, in_feat] (None unless want_dx) and their elementwise bounds.  x and the masked
     G * g_scale (one multiply in the dtype of G: fp32 as in the kernels, float64 in the CPU oracle test) enter the
     weight gradient, ``Wd`` [M, K, Cout] the input gradient.  round_w / round_d: the masked gradient is rounded to
-    bf16 before the weight / input gradient GEMM; bias_rounded: the bias gradient sums those rounded values."""
+    bf16 before the weight / input gradient GEMM; bias_rounded: the bias gradient sums those rounded values.
+    scale_after (weight gradient only): the masked G is rounded unscaled and g_scale multiplies the sums."""
+    assert not (scale_after and want_dx)
+    post = float(g_scale) if scale_after else 1.0
+    if scale_after:
+        g_scale = 1.0
     T, P, E, _ = x.shape
     dW = torch.zeros(M, ly.K, ly.Cout, dtype=torch.float64)
     bW = torch.zeros_like(dW)
@@ -207,11 +219,11 @@ def backward_ref(ly, x, G, bits, Wd, acts, M, g_scale, round_w=False, round_d=Fa
             gm = torch.where(bits[p][a], gp, torch.zeros_like(gp))
             gr = gm.to(torch.bfloat16).double() if (round_w or round_d or bias_rounded) else None
             gw = gr if round_w else gm.double()
-            dW[j] += ly.in_scale * (A.t() @ gw)
-            bW[j] += ly.in_scale * (A.abs().t() @ gw.abs())
+            dW[j] += post * ly.in_scale * (A.t() @ gw)
+            bW[j] += post * ly.in_scale * (A.abs().t() @ gw.abs())
             gb = gr if bias_rounded else gm.double()
-            db[j] += gb.sum(0)
-            bb[j] += gb.abs().sum(0)
+            db[j] += post * gb.sum(0)
+            bb[j] += post * gb.abs().sum(0)
             users[j] += 1
             if want_dx:
                 gd = gr if round_d else gm.double()
